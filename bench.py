@@ -3,8 +3,14 @@
 reference's schedule comparison (GPipe vs 1F1B vs Interleaved1F1B) in the same call.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model gpt2-small]
-                    [--schedule 1F1B] [--schedules all] [--ref-fp32 auto]
-                    [--mbs MBS] [--seq 1024] [--microbatches M]
+                    [--schedule 1F1B] [--mbs MBS] [--seq 1024] [--microbatches M]
+                    [--dump-outputs DIR] [--full [--schedules all] [--ref-fp32 auto]]
+
+A plain run measures the headline only: it sets up, runs W warmup steps, times K steps,
+writes the last timed step's outputs if ``--dump-outputs DIR`` is given (dump_outputs: loss,
+per-microbatch losses and a fixed sample of the updated parameters as float32 ``.npy``;
+the same arguments give the same inputs every run) and prints the result line.  ``--full``
+adds everything else listed below (items 2-4 and the profiled bubble step).
 
 N GPUs = N pipeline stages (PP=N, one process per GPU); for N>1 the driver launches it
 with torch.distributed.run (if launched without it, this script re-launches itself under
@@ -19,7 +25,8 @@ overlap them; profiles/r3_bench_mbs64_ab.txt).  Each timed step is a full traini
 all microbatch forwards/backwards through the lowered schedule, p2p of activations and
 gradients, grad-norm clip and the fused AdamW update.
 
-One call measures, each in a fresh child process group (so one can never cost another):
+One ``--full`` call measures, each in a fresh child process group (so one can never cost
+another; a plain call stops after item 1 and reports no bubble):
   1. the headline (``value``, ``ms_per_step``, ``config``): ``--schedule`` (auto: the best
      planned of GPipe / 1F1B / Interleaved1F1B / ZBH1, ``config.schedule_choice``);
   2. ``schedules``: GPipe, 1F1B, Interleaved1F1B (v=2) and ZBH1 on the same model, batch and
@@ -203,7 +210,35 @@ def parse(argv=None):
                     help="model of the schedule comparison (``schedules``): 'same', a name ('name:L' = L layers), or "
                          "auto: the headline model, unless it cannot interleave two chunks per rank at this pipeline "
                          "size (fewer than 2P layers: GPT-2 small at P = 8), then the smallest GPT-2 that can")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the profiled bubble step, the other "
+                         "schedules (--schedules), the reference's fp32 config (--ref-fp32) and BASELINE.json's "
+                         "named configs (--base-configs); without it only the headline is set up, warmed up and "
+                         "timed")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned and left behind as "
+                         "DIR/<name>.npy (float32): loss, microbatch_losses, params_sample (dump_outputs)")
+    a = ap.parse_args(argv)
+    if not a.full:
+        # a plain run: the headline's setup, warmup and timed steps, nothing else
+        a.schedules, a.ref_fp32, a.base_configs, a.no_bubble = "none", "0", "0", True
+    return a
+
+
+def drop_option(argv, name: str) -> list:
+    """``argv`` without the option ``name`` and its value ("name value" or "name=value")."""
+    out, skip = [], False
+    for x in argv:
+        if skip:
+            skip = False
+            continue
+        if x == name:
+            skip = True
+            continue
+        if x.startswith(name + "="):
+            continue
+        out.append(x)
+    return out
 
 
 def model_layers(name: str):
@@ -369,6 +404,7 @@ def plan_phases(a, argv) -> list:
     headline's attempts first, then every other schedule of ``--schedules`` on the same
     model/config, then the reference's fp32 config per schedule."""
     tags = [(f"h{k}", "headline", list(argv), a.schedule) for k in range(max(1, a.max_attempts))]
+    argv = drop_option(argv, "--dump-outputs")      # the headline's outputs only
     # every comparison entry gets a slot (on the comparison model: compare_model); the one the
     # headline ran (known once it is in: same model, planned lag) is skipped.  One GPU has no
     # pipeline and no head lag: "1F1B+lag" would repeat "1F1B"
@@ -834,6 +870,42 @@ def _plain_summary():
             "mipipe": sum(1 for v in ch.values() if v == "hip")}
 
 
+DUMP_BUDGET_BYTES = 48 << 20     # params_sample over all ranks (the whole dump stays under 64 MB)
+DUMP_PER_TENSOR = 32768          # sampled elements per parameter tensor at most
+
+
+def dump_outputs(path: str, trainer, loss, rank: int, world: int) -> None:
+    """``--dump-outputs``: what a caller of the timed path holds after the last timed step, as
+    float32 ``.npy`` files -- ``loss`` (train_step's return value) and ``microbatch_losses``
+    (trainer.last_losses) from the rank that has them, and ``params_sample``: this rank's
+    updated master parameters (trainer.state_dict(), names sorted), from each tensor a fixed
+    sample of at most DUMP_PER_TENSOR elements (indices from a generator seeded per tensor
+    position; a smaller tensor whole), concatenated.  Ranks past the first write
+    ``<name>.rank<r>.npy``.  Same arguments, same inputs and same sample from run to run."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    sfx = "" if rank == 0 or world == 1 else f".rank{rank}"
+
+    def save(name, t):
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), t.detach().to("cpu", torch.float32).contiguous().numpy())
+    if loss is not None:
+        save("loss", loss.reshape(1))
+        save("microbatch_losses", torch.stack([x.reshape(()) for x in trainer.last_losses]))
+    sd = trainer.state_dict()
+    names = sorted(sd)
+    cap = max(1, min(DUMP_PER_TENSOR, DUMP_BUDGET_BYTES // 4 // max(1, world) // max(1, len(names))))
+    parts = []
+    for i, n in enumerate(names):
+        flat = sd[n].reshape(-1)
+        if flat.numel() > cap:
+            g = torch.Generator().manual_seed(977 + i)
+            idx = torch.randint(0, flat.numel(), (cap,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.to("cpu", torch.float32))
+    save("params_sample", torch.cat(parts) if parts else torch.zeros(0))
+
+
 def run(a) -> None:
     import torch
     import torch.distributed as dist
@@ -929,6 +1001,9 @@ def run(a) -> None:
     tokens_per_step = gb * a.seq
     value = tokens_per_step * a.steps / elapsed
     ms = elapsed / a.steps * 1e3
+    if a.dump_outputs:
+        with wd.step(init_to):      # before the profiled step below runs the optimizer once more
+            dump_outputs(a.dump_outputs, trainer, loss if a.steps > 0 else None, rank, world)
 
     # one extra profiled step on the same (native tape) path: measured bubble
     bubble = per_rank = None
@@ -1202,17 +1277,7 @@ def main():
     if os.environ.get("MIPIPE_BENCH_CHILD") != "1" and not a.no_supervise and a.phase == "sched":
         # (an explicit internal --phase runs that phase here, e.g. under a profiler)
         # drop a --graphs the supervisor will set per attempt
-        child_argv, skip = [], False
-        for x in argv:
-            if skip:
-                skip = False
-                continue
-            if x == "--graphs":
-                skip = True
-                continue
-            if x.startswith("--graphs="):
-                continue
-            child_argv.append(x)
+        child_argv = drop_option(argv, "--graphs")
         sys.exit(supervise(a, child_argv))
     if a.phase == "ref":
         run_ref(a)

@@ -71,7 +71,7 @@ def test_baseline_configs_are_planned_last_at_their_gpu_count():
     try:
         for world, n in ((4, 1), (8, 3), (2, 0)):
             os.environ["WORLD_SIZE"] = str(world)
-            a = bench.parse(["--base-configs", "1", "--ref-fp32", "1"])
+            a = bench.parse(["--full", "--base-configs", "1", "--ref-fp32", "1"])
             ph = bench.plan_phases(a, ["--steps", "3"])
             kinds = [k for _, k, _, _ in ph]
             assert kinds.count("base") == n
@@ -84,7 +84,8 @@ def test_baseline_configs_are_planned_last_at_their_gpu_count():
             if not os.path.exists("/dev/kfd"):
                 assert not [p for p in bench.plan_phases(a, []) if p[1] == "base"]
         os.environ["WORLD_SIZE"] = "8"
-        assert any("llama3-8b" in x for x in bench.plan_phases(bench.parse(["--base-configs", "1"]), [])[-1][2])
+        a = bench.parse(["--full", "--base-configs", "1"])
+        assert any("llama3-8b" in x for x in bench.plan_phases(a, [])[-1][2])
     finally:
         if old is None:
             os.environ.pop("WORLD_SIZE", None)
@@ -146,7 +147,7 @@ def test_bench_eight_ranks_gpt2_small_layout():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--mbs", "1",
-           "--seq", "32", "--vocab", "512", "--base-configs", "0"]
+           "--seq", "32", "--vocab", "512", "--full", "--base-configs", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -173,6 +174,45 @@ def test_bench_default_batch_is_128_sequences_per_gpu():
     c = out["config"]
     assert (c["micro_batch"], c["microbatches"], c["global_batch"]) == (64, 2, 128)
     assert out["scaling"] == "weak" and out["n_gpus"] == 1
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full nothing beside the headline is planned or measured (no other schedule,
+    no reference phase, no baseline config, no profiled bubble step), whatever the other
+    options say; --dump-outputs writes the last timed step's loss, per-microbatch losses and
+    the parameter sample as float32 .npy, identical from run to run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--schedules", "all", "--ref-fp32", "1", "--base-configs", "1"])
+    assert {k for _, k, _, _ in bench.plan_phases(a, [])} == {"headline"} and a.no_bubble
+    a = bench.parse(["--full", "--ref-fp32", "1"])
+    assert {k for _, k, _, _ in bench.plan_phases(a, ["--dump-outputs", "d"])} == {"headline", "sched", "ref"}
+    assert all(("--dump-outputs" in argv) == (k == "headline") for _, k, argv, _ in bench.plan_phases(
+        a, ["--dump-outputs", "d"]))
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    dumps = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "gpt2-tiny", "--vocab", "256",
+               "--seq", "16", "--mbs", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd="/tmp")
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0 and out["unit"] == "tokens/s"
+        assert out["bubble_fraction"] is None and "reference_fp32" not in out and "baseline_configs" not in out
+        assert list(out["schedules"]) == [out["config"]["schedule"]]     # the headline's own entry, nothing measured
+        dumps.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+        assert set(dumps[-1]) == {"loss.npy", "microbatch_losses.npy", "params_sample.npy"}
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in dumps[-1].values())
+        assert dumps[-1]["loss.npy"][0] == pytest.approx(out["last_loss"], abs=1e-4)
+        assert dumps[-1]["microbatch_losses.npy"].shape == (out["config"]["microbatches"],)
+        assert 0 < dumps[-1]["params_sample.npy"].nbytes <= 64 << 20
+    for f in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][f], dumps[1][f])
 
 
 def test_bench_pipeline_plans_the_microbatch_size():
@@ -202,7 +242,7 @@ def test_bench_four_ranks_measures_all_three_schedules():
     env = dict(os.environ, OMP_NUM_THREADS="1", MASTER_PORT=str(free_port()))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--base-configs", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--full", "--base-configs", "0",
            "--compare-model", "same"] + ARGS[:-2]
     t0 = time.monotonic()
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env, cwd="/tmp")
@@ -328,8 +368,8 @@ def test_bench_eight_ranks_reference_at_published_pipeline_sizes():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--mbs",
-           "1", "--seq", "32", "--vocab", "512", "--model", "gpt2-tiny", "--base-configs", "0", "--schedules", "none",
-           "--ref-fp32", "1", "--ref-grid", "4,4", "--no-bubble"]
+           "1", "--seq", "32", "--vocab", "512", "--model", "gpt2-tiny", "--full", "--base-configs", "0",
+           "--schedules", "none", "--ref-fp32", "1", "--ref-grid", "4,4", "--no-bubble"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=540, env=env, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -357,7 +397,7 @@ def test_bench_eight_ranks_compares_the_schedules_it_names():
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--mbs", "1",
            "--seq", "32", "--vocab", "512", "--model", "gpt2-tiny", "--compare-model", "gpt2-tiny:16",
-           "--base-configs", "0", "--ref-fp32", "0", "--no-bubble"]
+           "--full", "--base-configs", "0", "--ref-fp32", "0", "--no-bubble"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=540, env=env, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
