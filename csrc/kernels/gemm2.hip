@@ -152,14 +152,32 @@ __device__ __forceinline__ void wait_vmcnt() {
 
 // ---- epilogue: one wave-row group at a time through LDS -> coalesced 16-byte bias /
 // residual / activation / store, or lane-consecutive f32 atomics for split-K
+// -DMP_EPI_ROLLED (tools/build_ext.py --variant rolled -DMP_EPI_ROLLED) builds the epilogue
+// as it was before the in-flight store loop, for A/B on one box: a rolled chunk loop that
+// loads at the point of use, and the p_drop test once per element
+#ifdef MP_EPI_ROLLED
+constexpr bool EPI_ROLLED = true, EPI_DROP_PER_ELEM = true;
+#else
+constexpr bool EPI_ROLLED = false, EPI_DROP_PER_ELEM = false;
+#endif
+
+constexpr bool epi_has_bias(int epi) {
+  return epi == EPI_BIAS || epi == EPI_BIAS_GELU || epi == EPI_BIAS_RELU || epi == EPI_BIAS_RES;
+}
+// epilogues that read a second [M, N] stream: the residual R, or the saved activation input AUX
+constexpr bool epi_has_row(int epi) {
+  return epi == EPI_BIAS_RES || epi == EPI_RES || epi == EPI_DGELU || epi == EPI_DRELU;
+}
+
 // the fused epilogue of 8 consecutive outputs (row gr, columns gc..gc+7) -> bf16 C
+// bv: the bias chunk bias[gc..gc+7]; xv: the row-input chunk (R or AUX at row gr, columns
+// gc..gc+7) -- loaded by the caller (each read only by the epilogues that have one), so the
+// store loop can keep them in flight ahead of the chunk that consumes them
 template <int EPI>
-__device__ __forceinline__ void epi_store8(float (&v)[8], int gr, int gc, bf16_t* __restrict__ C, int64_t ldc,
-                                           const bf16_t* __restrict__ bias, const bf16_t* __restrict__ R,
-                                           int64_t ldr, bf16_t* __restrict__ AUX, int64_t ldx, float p_drop,
-                                           uint64_t seed) {
-  if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_RES) {
-    u16x8 bv = *reinterpret_cast<const u16x8*>(bias + gc);
+__device__ __forceinline__ void epi_apply8(float (&v)[8], int gr, int gc, bf16_t* __restrict__ C, int64_t ldc,
+                                           const u16x8& bv, const u16x8& xv, bf16_t* __restrict__ AUX, int64_t ldx,
+                                           float p_drop, uint64_t seed) {
+  if constexpr (epi_has_bias(EPI)) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] += bf2f(bv[e]);
   }
@@ -182,22 +200,29 @@ __device__ __forceinline__ void epi_store8(float (&v)[8], int gr, int gc, bf16_t
       }
       // dropout after the activation (the reference FFN's drop(relu(.))), mask index =
       // element index of the contiguous output, as act_fwd / act_bwd regenerate it
-      if (p_drop > 0.f) v[e] *= dropout_scale(seed, (uint64_t)gr * ldc + gc + e, p_drop);
+      if (EPI_DROP_PER_ELEM && p_drop > 0.f) v[e] *= dropout_scale(seed, (uint64_t)gr * ldc + gc + e, p_drop);
+    }
+    // p_drop is wave-uniform: one branch per chunk (it compiled to one per element inside the loop)
+    if (!EPI_DROP_PER_ELEM && p_drop > 0.f) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] *= dropout_scale(seed, (uint64_t)gr * ldc + gc + e, p_drop);
     }
     *reinterpret_cast<u16x8*>(AUX + (int64_t)gr * ldx + gc) = sv;
   }
   if constexpr (EPI == EPI_BIAS_RES || EPI == EPI_RES) {
-    u16x8 rv = *reinterpret_cast<const u16x8*>(R + (int64_t)gr * ldr + gc);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] += bf2f(rv[e]);
+    for (int e = 0; e < 8; ++e) v[e] += bf2f(xv[e]);
   }
   if constexpr (EPI == EPI_DGELU || EPI == EPI_DRELU) {
-    u16x8 xv = *reinterpret_cast<const u16x8*>(AUX + (int64_t)gr * ldx + gc);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float x = bf2f(xv[e]);   // GELU: the saved derivative; ReLU: the pre-activation
       v[e] *= EPI == EPI_DGELU ? x : (x > 0.f ? 1.f : 0.f);
-      if (p_drop > 0.f) v[e] *= dropout_scale(seed, (uint64_t)gr * ldc + gc + e, p_drop);
+      if (EPI_DROP_PER_ELEM && p_drop > 0.f) v[e] *= dropout_scale(seed, (uint64_t)gr * ldc + gc + e, p_drop);
+    }
+    if (!EPI_DROP_PER_ELEM && p_drop > 0.f) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] *= dropout_scale(seed, (uint64_t)gr * ldc + gc + e, p_drop);
     }
   }
   u16x8 o;
@@ -213,10 +238,25 @@ __device__ __forceinline__ void epi_store8(float (&v)[8], int gr, int gc, bf16_t
 #endif
 }
 
+// the same with the bias / row-input chunks loaded here, at the point of use (the rolled
+// store loop and the split-K reduce pass)
+template <int EPI>
+__device__ __forceinline__ void epi_store8(float (&v)[8], int gr, int gc, bf16_t* __restrict__ C, int64_t ldc,
+                                           const bf16_t* __restrict__ bias, const bf16_t* __restrict__ R,
+                                           int64_t ldr, bf16_t* __restrict__ AUX, int64_t ldx, float p_drop,
+                                           uint64_t seed) {
+  u16x8 bv = {}, xv = {};
+  if constexpr (epi_has_bias(EPI)) bv = *reinterpret_cast<const u16x8*>(bias + gc);
+  if constexpr (EPI == EPI_BIAS_RES || EPI == EPI_RES) xv = *reinterpret_cast<const u16x8*>(R + (int64_t)gr * ldr + gc);
+  if constexpr (EPI == EPI_DGELU || EPI == EPI_DRELU) xv = *reinterpret_cast<const u16x8*>(AUX + (int64_t)gr * ldx + gc);
+  epi_apply8<EPI>(v, gr, gc, C, ldc, bv, xv, AUX, ldx, p_drop, seed);
+}
+
 // accumulator layout of the 32x32x16 engines: acc[i][j] element r -> wave-local
 // row 32 i + (r & 3) + 8 (r >> 2) + 4 hl, column wn + 32 j + l32
 template <int WTM, int WTN>
 struct Stage32 {
+  static constexpr bool M16 = false;
   f32x16 (&acc)[WTM][WTN];
   int wn, hl, l32;
   __device__ __forceinline__ void operator()(float* ct, int CP) const {
@@ -237,6 +277,7 @@ struct Stage32 {
 // row 16 i + 4 (lane >> 4) + r, column wn + 16 j + (lane & 15)
 template <int TM, int TN>
 struct Stage16 {
+  static constexpr bool M16 = true;
   f32x4 (&acc)[TM][TN];
   int wn, lane;
   __device__ __forceinline__ void operator()(float* ct, int CP) const {
@@ -274,8 +315,53 @@ __device__ __forceinline__ void epilogue(const StageF& stage, char* smem, int m0
   constexpr bool CS_OK = !ACC;
   const bool cs = CS_OK && WS != nullptr;
   float csum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  // In-flight store loop (fused bf16 epilogues, whole tiles whose chunk count is a multiple
+  // of the thread count: 256x256, 256x128, 128x128, 64x64).  gfx950 counts loads and stores
+  // in one vmcnt, so a rolled loop that loads a chunk's bias / row input at its point of use
+  // waits, every iteration, for the previous iteration's store to be acknowledged as well:
+  // NL serial round trips of store ack + HBM load per pass.  Here the bias chunk (a thread's
+  // columns are fixed) is loaded once, all NL row-input chunks of a pass are issued before
+  // the staging barrier, and the chunk loop is unrolled and unguarded, so chunk u waits
+  // vmcnt(NL - 1): row load u landed, the younger loads and the u stores of this pass stay
+  // in flight.  (Behind a per-chunk range guard the compiler counts the minimum over the
+  // paths that skipped their stores, vmcnt(NL - 1 - u), which in the in-order counter covers
+  // this pass's first stores from chunk NL / 2 on -- so tiles on the M / N edge keep the
+  // rolled loop, as do EPI_NONE, which has no load to wait for, BN = 192 (NTE = 504), the
+  // stream-K owner (PARTS) and the f32 accumulate paths.)  Arithmetic per element and its
+  // order are the rolled loop's.
+  // (the 32x32x16 builds of the 256x256 tile, MIPIPE_GEMM_M16=0, also keep the rolled loop:
+  // with the 8 row chunks in registers beside the accumulators their dGELU build spills)
+  constexpr bool INFLIGHT = !EPI_ROLLED && !ACC && !PARTS && EPI != EPI_NONE && (RG * CH) % NTE == 0 && NTE == NTH &&
+                            (StageF::M16 || BM * BN < 256 * 256);
+  constexpr int NL = INFLIGHT ? RG * CH / NTH : 1;   // chunks per thread and pass
+  constexpr int RSTEP = NTH / CH;                    // tile rows between a thread's consecutive chunks
+  const bool inflight = INFLIGHT && m0 + BM <= M && n0 + BN <= N;
+  // without a row input there is nothing to keep in flight: with the bias hoisted the loop
+  // has no load and so no vmcnt wait, and it stays rolled (unrolled, the bias+GELU build of
+  // gemm3 -- the accumulators of wave row 1 stay live through pass 0 -- spills)
+  constexpr int UNR = epi_has_row(EPI) ? NL : 1;
+  const int trow = (int)threadIdx.x / CH, tgc = n0 + ((int)threadIdx.x % CH) * 8;
+  u16x8 bvec = {};
+  if constexpr (INFLIGHT && epi_has_bias(EPI)) {
+    if (inflight) bvec = *reinterpret_cast<const u16x8*>(bias + tgc);
+  }
 #pragma unroll 1
   for (int pass = 0; pass < WM; ++pass) {
+    u16x8 xrow[NL] = {};
+    if constexpr (INFLIGHT && epi_has_row(EPI)) {
+      // Aliasing: R may be C itself (the in-place `linear_dx(..., residual=dh, out=dh)` of
+      // models/native.py's cross-attention backward; every other caller in ops/kernels.py and
+      // models/native.py passes R / AUX distinct from C).  A thread reads here exactly the
+      // chunks it overwrites itself later in this pass, and no other thread writes them, so
+      // in-place use stays correct.
+      if (inflight) {
+        const bf16_t* xp = (EPI == EPI_DGELU || EPI == EPI_DRELU) ? AUX : R;
+        const int64_t ldxp = (EPI == EPI_DGELU || EPI == EPI_DRELU) ? ldx : ldr;
+#pragma unroll
+        for (int u = 0; u < NL; ++u)
+          xrow[u] = *reinterpret_cast<const u16x8*>(xp + (int64_t)(m0 + pass * RG + trow + u * RSTEP) * ldxp + tgc);
+      }
+    }
     if (wr == pass) stage(ct, CP);
     __syncthreads();
     if constexpr (!ACC && PARTS) {
@@ -334,6 +420,24 @@ __device__ __forceinline__ void epilogue(const StageF& stage, char* smem, int m0
         continue;
       }
     }
+    if (inflight) {
+      bf16_t* C = reinterpret_cast<bf16_t*>(Cv);
+#pragma unroll UNR
+      for (int u = 0; u < NL; ++u) {
+        const int row = trow + u * RSTEP, gr = rbase + row;
+        float v[8];
+        const float4 lo = *reinterpret_cast<const float4*>(ct + row * CP + (tgc - n0));
+        const float4 hi = *reinterpret_cast<const float4*>(ct + row * CP + (tgc - n0) + 4);
+        v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] *= alpha;
+        epi_apply8<EPI>(v, gr, tgc, C, ldc, bvec, xrow[epi_has_row(EPI) ? u : 0], AUX, ldx, p_drop, seed);
+        if (cs) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) csum[e] += v[e];
+        }
+      }
+    } else
     for (int idx = threadIdx.x < NTE ? (int)threadIdx.x : RG * CH; idx < RG * CH; idx += NTE) {
       const int row = idx / CH, c8 = (idx % CH) * 8;
       const int gr = rbase + row, gc = n0 + c8;

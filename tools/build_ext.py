@@ -2,6 +2,8 @@
 
     python tools/build_ext.py [--force] [-j N]
     python tools/build_ext.py --asan-host     # host runtime under ASan/UBSan, built and run
+    python tools/build_ext.py --variant rolled -DMP_EPI_ROLLED   # A/B build (_C_rolled.so) with the
+                                              # rolled GEMM epilogue; load it with MIPIPE_EXT_VARIANT=rolled
 
 
 Each ``csrc/kernels/*.hip`` is compiled by ``hipcc --offload-arch=gfx950`` into an
