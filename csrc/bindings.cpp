@@ -49,6 +49,11 @@ int mp_attn_bwd(const void* q, const void* k, const void* v, const void* o, cons
                 int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t dq_stride,
                 int64_t dk_stride, int64_t dv_stride, int causal, float scale, float p_drop, uint64_t seed,
                 float* csq, float* csk, float* csv, hipStream_t st);
+int mp_attn_decode(const void* q, const void* k, const void* v, const int* lens, void* o, float* ws, int B, int H,
+                   int Hkv, int D, int Smax, int max_len, int64_t q_stride, int64_t k_bs, int64_t k_ts, int64_t v_bs,
+                   int64_t v_ts, int64_t o_stride, float scale, int splits, hipStream_t st);
+int mp_attn_decode_plan(int B, int Hkv, int max_len);
+int64_t mp_attn_decode_ws_floats(int B, int H, int D, int splits);
 int mp_attn_f32_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int Sq, int Sk, int H,
                     int Hkv, int D, int64_t qs, int64_t ks, int64_t vs, int64_t os, int causal, float scale,
                     float p_drop, uint64_t seed, hipStream_t st);
@@ -369,6 +374,48 @@ void attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o
         "attn_bwd");
 }
 
+// Decode attention (attention_decode.hip): one query row per sequence against its KV cache.
+// q/o: [B, H*D] row views; k_cache/v_cache: [B, Smax, Hkv*D] views with unit inner stride;
+// lens: int32 [B] on the device (valid keys per sequence); max_len >= max(lens) sizes the
+// grid; splits: 0 = planner, n > 0 forces n.  Returns the split count used.
+int64_t attn_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor lens,
+                    torch::Tensor o, int64_t H, int64_t Hkv, int64_t D, int64_t max_len, double scale,
+                    int64_t splits) {
+  req(lens, torch::kInt32, "lens");
+  for (const torch::Tensor* t : {&q, &k_cache, &v_cache, &o})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16, "attn_decode: q/k_cache/v_cache/o must be bf16 GPU tensors");
+  TORCH_CHECK(q.dim() == 2 && o.dim() == 2 && q.stride(1) == 1 && o.stride(1) == 1, "attn_decode: q/o are [B, H*D] rows");
+  TORCH_CHECK(k_cache.dim() == 3 && v_cache.dim() == 3 && k_cache.stride(2) == 1 && v_cache.stride(2) == 1,
+              "attn_decode: caches are [B, Smax, Hkv*D] with a unit inner stride");
+  const int64_t B = q.size(0), Smax = k_cache.size(1);
+  TORCH_CHECK(D == 64 || D == 128, "attn_decode: head_dim ", D, " is not supported (64 or 128)");
+  TORCH_CHECK(Hkv >= 1 && H >= 1 && H % Hkv == 0 && H / Hkv <= 8,
+              "attn_decode: H = ", H, ", Hkv = ", Hkv, " is not supported (H % Hkv == 0, H / Hkv <= 8)");
+  TORCH_CHECK(q.size(1) == H * D && o.size(0) == B && o.size(1) == H * D, "attn_decode: q/o shape");
+  TORCH_CHECK(k_cache.size(0) == B && v_cache.size(0) == B && v_cache.size(1) == Smax &&
+                  k_cache.size(2) == Hkv * D && v_cache.size(2) == Hkv * D, "attn_decode: cache shape");
+  TORCH_CHECK(lens.numel() == B, "attn_decode: lens must hold one length per sequence");
+  TORCH_CHECK(max_len >= 1 && max_len <= Smax, "attn_decode: max_len ", max_len, " outside [1, ", Smax, "]");
+  TORCH_CHECK(splits >= 0 && splits <= max_len && splits <= 256, "attn_decode: splits ", splits,
+              " outside [0, min(max_len, 256)]");
+  TORCH_CHECK(B >= 1 && B <= 65535 && Hkv <= 65535, "attn_decode: batch / KV heads exceed the grid");
+  const auto aligned = [](const torch::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; };
+  TORCH_CHECK(aligned(q) && aligned(k_cache) && aligned(v_cache) && q.stride(0) % 8 == 0 &&
+                  k_cache.stride(0) % 8 == 0 && k_cache.stride(1) % 8 == 0 && v_cache.stride(0) % 8 == 0 &&
+                  v_cache.stride(1) % 8 == 0,
+              "attn_decode: q / cache rows must be 16-byte aligned");
+  const int ns = splits > 0 ? (int)splits : mp_attn_decode_plan((int)B, (int)Hkv, (int)max_len);
+  // per-split partial outputs + (max, sum): from the caching allocator on the current stream
+  torch::Tensor ws = torch::empty({mp_attn_decode_ws_floats((int)B, (int)H, (int)D, ns)},
+                                  q.options().dtype(torch::kFloat32));
+  check(mp_attn_decode(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), lens.data_ptr<int>(), o.data_ptr(),
+                       ws.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)D, (int)Smax, (int)max_len, q.stride(0),
+                       k_cache.stride(0), k_cache.stride(1), v_cache.stride(0), v_cache.stride(1), o.stride(0),
+                       (float)scale, ns, cur_stream()),
+        "attn_decode");
+  return ns;
+}
+
 // C[M,N] (+)= alpha * op(A) @ op(B) with fused epilogue.
 //   A: [M,K] row-major (transA=0) or [K,M] (transA=1); B: [N,K] (transB=0, "NT") or [K,N] (transB=1)
 void gemm(torch::Tensor A, torch::Tensor B, torch::Tensor C, c10::optional<torch::Tensor> bias,
@@ -650,6 +697,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope", &rope);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
+  m.def("attn_decode", &attn_decode, pybind11::arg("q"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
+        pybind11::arg("lens"), pybind11::arg("o"), pybind11::arg("H"), pybind11::arg("Hkv"), pybind11::arg("D"),
+        pybind11::arg("max_len"), pybind11::arg("scale"), pybind11::arg("splits") = 0);
+  m.def("attn_decode_plan", [](int64_t B, int64_t Hkv, int64_t max_len) {
+    return mp_attn_decode_plan((int)B, (int)Hkv, (int)max_len);
+  }, "key splits the decode attention picks for B sequences x Hkv KV heads over max_len keys");
   m.def("gemm", &gemm);
   m.def("lane_merge", &lane_merge, pybind11::arg("g0"), pybind11::arg("lanes"), pybind11::arg("sumsq") = pybind11::none());
   m.def("gemm_tt_grouped", &gemm_tt_grouped, pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("C"),

@@ -10,3 +10,4 @@ stash, and DP x PP gradient all-reduce overlapped with the pipeline flush.
 __version__ = "0.1.0"
 
 from . import parallel  # noqa: F401
+from .models.generate import Generator, KVCache  # noqa: F401

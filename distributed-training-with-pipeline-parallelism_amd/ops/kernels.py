@@ -893,6 +893,47 @@ def attn_bwd(q, k, v, o, do, lse, dq, dk, dv, B: int, Sq: int, Sk: int, H: int, 
     return dq, dk, dv
 
 
+def attn_decode_plan(B: int, Hkv: int, max_len: int) -> int:
+    """Key splits :func:`attn_decode` picks (``splits=0``) for ``B`` sequences x ``Hkv`` KV
+    heads over caches of up to ``max_len`` keys (csrc/kernels/attention_decode.hip)."""
+    return int(_ext().attn_decode_plan(int(B), int(Hkv), int(max_len)))
+
+
+def attn_decode(q, k_cache, v_cache, lens, o, H: int, Hkv: int, D: int, scale: Optional[float] = None,
+                splits: int = 0, max_len: Optional[int] = None):
+    """Attention of one new token per sequence over its KV cache.  q/o: [B, H*D] row views
+    (q is a slice of the packed qkv row); k_cache/v_cache: [B, Smax, Hkv*D] views; lens:
+    int32 [B] on q's device, the valid keys per sequence including the current token.
+    Causal by construction: a decode query sees every cached key.  ``max_len`` (a host
+    int >= max(lens), default Smax) sizes the GPU grid; ``splits``: 0 = the kernel's
+    planner, n > 0 forces n key splits.  Rows at positions >= lens[b] never enter the
+    result.  Writes o."""
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    if D not in (64, 128) and _gpu(q):
+        raise ValueError(f"attn_decode: head_dim {D} is not supported by the HIP kernel (64 or 128)")
+    if H % Hkv or (_gpu(q) and H // Hkv > 8):
+        raise ValueError(f"attn_decode: H = {H}, Hkv = {Hkv} is not supported (H % Hkv == 0, H / Hkv <= 8)")
+    if lens.dtype != torch.int32 or lens.device != q.device:
+        raise ValueError("attn_decode: lens must be an int32 tensor on q's device")
+    B, Smax = q.shape[0], k_cache.shape[1]
+    max_len = Smax if max_len is None else int(max_len)
+    if _gpu(q):
+        _ext().attn_decode(q, k_cache, v_cache, lens, o, int(H), int(Hkv), int(D), max_len, float(scale), int(splits))
+        return o
+    rep = H // Hkv
+    for b, n in enumerate(lens.tolist()):
+        n = max(0, min(int(n), Smax))
+        if n == 0:
+            o[b, : H * D].zero_()
+            continue
+        Q = q[b, : H * D].float().reshape(H, 1, D)
+        K = k_cache[b, :n, : Hkv * D].float().reshape(n, Hkv, D).permute(1, 0, 2).repeat_interleave(rep, 0)
+        V = v_cache[b, :n, : Hkv * D].float().reshape(n, Hkv, D).permute(1, 0, 2).repeat_interleave(rep, 0)
+        p = torch.softmax((Q @ K.transpose(-1, -2)) * scale, -1)
+        o[b, : H * D].copy_((p @ V).reshape(H * D).to(o.dtype))
+    return o
+
+
 # ======================================================================================
 # optimizer
 # ======================================================================================

@@ -186,6 +186,36 @@ def load_checkpoint(trainer, path: str, load_optimizer: bool = True, strict: boo
     return man
 
 
+def load_weights(arenas, path: str, strict: bool = True) -> dict:
+    """Weights-only load: copy the f32 master tensors of a checkpoint written at any PP / DP
+    degree or head mode into ``arenas`` (each takes exactly the FQNs it owns, whichever
+    shard holds them -- a tied head kept in ``head.safetensors`` is found as
+    ``tok_embeddings.weight``), then refresh their working copies.  No trainer, optimizer
+    or process group is involved (inference: models/generate.py).  Returns the manifest."""
+    from safetensors import safe_open
+
+    man = read_manifest(path)
+    idx = _index(path, man)
+    handles = {}
+    missing = []
+    for arena in arenas:
+        with arena.unsharded():
+            for name in arena.order:
+                fn = idx.get(name)
+                if fn is None:
+                    missing.append(name)
+                    continue
+                if fn not in handles:
+                    handles[fn] = safe_open(os.path.join(path, fn), framework="pt")
+                t = handles[fn].get_tensor(name)
+                arena.master_view(name).copy_(t.reshape(arena.specs[name].shape).to(arena.device, torch.float32))
+            arena.sync_w16()
+    handles.clear()
+    if strict and missing:
+        raise KeyError(f"checkpoint {path} lacks {len(missing)} tensors, e.g. {missing[:4]}")
+    return man
+
+
 # ----------------------------------------------------------------------------------------
 # reference layout interop (helper:36-46, :78-91): global FQNs, unpadded vocabulary
 # ----------------------------------------------------------------------------------------

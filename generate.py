@@ -1,0 +1,55 @@
+"""Sample token ids from a mipipe checkpoint.
+
+    python generate.py --checkpoint DIR --prompt "1,2,3" --max-new-tokens 16
+    python generate.py --checkpoint DIR --prompt "1,2,3;7,8,9" --max-new-tokens 16 \
+        --temperature 0.8 --top-k 40 --seed 1 --device cuda
+
+The model configuration comes from the checkpoint's manifest; the weights are found by FQN,
+so a checkpoint written at any PP / DP degree loads into this single process.  Prompts are
+comma-separated token ids (train.py's data are ids; there is no tokenizer), several prompts
+of one shared length separated by ``;``.  Prints the prompt + generated ids, one sequence
+per line.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+
+
+def parse_prompts(text: str):
+    rows = [[int(t) for t in row.replace(" ", "").split(",") if t] for row in text.split(";") if row.strip()]
+    if not rows or any(not r for r in rows):
+        raise ValueError("--prompt: comma-separated token ids, prompts separated by ';'")
+    if len({len(r) for r in rows}) != 1:
+        raise ValueError("--prompt: the prompts of a batch must share one length")
+    return rows
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--checkpoint", required=True, help="directory written by save_checkpoint / train.py")
+    ap.add_argument("--prompt", required=True, help='token ids, e.g. "1,2,3" (";" between prompts)')
+    ap.add_argument("--max-new-tokens", type=int, default=16)
+    ap.add_argument("--temperature", type=float, default=0.0, help="0 = greedy")
+    ap.add_argument("--top-k", type=int, default=None)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", choices=("cpu", "cuda"), default=None, help="default: cuda when available")
+    a = ap.parse_args(argv)
+
+    import torch
+    import mipipe
+
+    rows = parse_prompts(a.prompt)
+    gen = mipipe.Generator.load(a.checkpoint, device=a.device)
+    bad = [t for r in rows for t in r if not 0 <= t < gen.cfg.vocab_size]
+    if bad:
+        raise ValueError(f"--prompt: token id {bad[0]} outside the vocabulary [0, {gen.cfg.vocab_size})")
+    out = gen.generate(torch.tensor(rows, dtype=torch.int64), a.max_new_tokens, temperature=a.temperature,
+                       top_k=a.top_k, seed=a.seed)
+    for r in out.tolist():
+        print(",".join(str(t) for t in r))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
