@@ -112,6 +112,22 @@ void req(const torch::Tensor& t, torch::ScalarType dt, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
+// req + the element count the launcher will index
+void reqn(const torch::Tensor& t, torch::ScalarType dt, int64_t n, const char* name) {
+  req(t, dt, name);
+  TORCH_CHECK(t.numel() == n, name, " has ", t.numel(), " elements, expected ", n);
+}
+
+// a [rows, width] position table (wpe / dwpe, RoPE cos / sin): token t reads row
+// t % S + pos_offset, so rows 0 .. min(T, S) + pos_offset - 1 must exist
+void req_pos_table(const torch::Tensor& t, int64_t width, int64_t T, int64_t S, int64_t pos_offset,
+                   const char* name) {
+  TORCH_CHECK(S >= 1 && pos_offset >= 0, name, ": S must be >= 1 and pos_offset >= 0");
+  const int64_t need = std::min(T, S) + pos_offset;
+  TORCH_CHECK(t.dim() == 2 && t.size(1) == width && t.size(0) >= need, name, " must be [>= ", need, ", ", width,
+              "] (min(T, S) + pos_offset rows), got ", t.sizes());
+}
+
 void norm_fwd(bool rms, torch::Tensor a, c10::optional<torch::Tensor> b, torch::Tensor w,
               c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> s_out, torch::Tensor y,
               c10::optional<torch::Tensor> mean, torch::Tensor rstd, double eps, double p, int64_t seed) {
@@ -157,14 +173,21 @@ int64_t norm_bwd(bool rms, torch::Tensor dy, torch::Tensor s, torch::Tensor w, c
   const int64_t pe = mp_norm_bwd_part_elems(rows, D);
   torch::Tensor part;
   if (pe > 0) part = torch::empty({pe}, dy.options().dtype(torch::kFloat32));
-  const int rc = mp_norm_bwd(f32, rms, dy.data_ptr(), s.data_ptr(), w.data_ptr(),
-                             mean.has_value() ? mean->data_ptr<float>() : nullptr, rstd.data_ptr<float>(),
-                             ptr_or_null(dres), ds.data_ptr(), mptr_or_null(dbranch), dw.data_ptr<float>(),
-                             dbias.has_value() ? dbias->data_ptr<float>() : nullptr,
-                             cs_res.has_value() ? cs_res->data_ptr<float>() : nullptr,
-                             cs_ds.has_value() ? cs_ds->data_ptr<float>() : nullptr, rows, D, (float)p,
-                             (uint64_t)seed, part.defined() ? part.data_ptr<float>() : nullptr, cur_stream());
-  if (rc == -3) return -3;
+  const auto run = [&](float* csr, float* css) {
+    return mp_norm_bwd(f32, rms, dy.data_ptr(), s.data_ptr(), w.data_ptr(),
+                       mean.has_value() ? mean->data_ptr<float>() : nullptr, rstd.data_ptr<float>(),
+                       ptr_or_null(dres), ds.data_ptr(), mptr_or_null(dbranch), dw.data_ptr<float>(),
+                       dbias.has_value() ? dbias->data_ptr<float>() : nullptr, csr, css, rows, D, (float)p,
+                       (uint64_t)seed, part.defined() ? part.data_ptr<float>() : nullptr, cur_stream());
+  };
+  const int rc = run(cs_res.has_value() ? cs_res->data_ptr<float>() : nullptr,
+                     cs_ds.has_value() ? cs_ds->data_ptr<float>() : nullptr);
+  if (rc == -3) {
+    // the launcher refused before launching anything: the backward itself still has to run,
+    // without the fused sums (the caller adds them in separate passes)
+    check(run(nullptr, nullptr), "norm_bwd");
+    return -3;
+  }
   check(rc, "norm_bwd");
   return 0;
 }
@@ -192,7 +215,8 @@ void embed_fwd(torch::Tensor idx, torch::Tensor wte, c10::optional<torch::Tensor
   if (wpe.has_value()) req(*wpe, out.scalar_type(), "wpe");
   const int D = wte.size(1);
   const int T = idx.numel();
-  TORCH_CHECK(out.numel() == (int64_t)T * D, "bad embed shapes");
+  TORCH_CHECK(wte.dim() == 2 && out.numel() == (int64_t)T * D, "bad embed shapes");
+  if (wpe.has_value()) req_pos_table(*wpe, D, T, S, pos_offset, "wpe");
   check(mp_embed_fwd(idx.data_ptr<int64_t>(), wte.data_ptr(), ptr_or_null(wpe), out.data_ptr(), T, S, D, pos_offset,
                      f32, cur_stream()),
         "embed_fwd");
@@ -207,6 +231,10 @@ void embed_bwd(torch::Tensor idx, torch::Tensor dout, torch::Tensor dwte, c10::o
   const int D = dwte.size(-1);
   const int T = idx.numel();
   TORCH_CHECK(dout.numel() == (int64_t)T * D, "bad embed_bwd shapes");
+  if (dwpe.has_value()) {
+    req(*dwpe, torch::kFloat32, "dwpe");
+    req_pos_table(*dwpe, D, T, S, pos_offset, "dwpe");
+  }
   check(mp_embed_bwd(idx.data_ptr<int64_t>(), dout.data_ptr(), dwte.data_ptr<float>(),
                      dwpe.has_value() ? dwpe->data_ptr<float>() : nullptr, T, S, D, pos_offset, f32, cur_stream()),
         "embed_bwd");
@@ -231,6 +259,7 @@ void lane_merge(torch::Tensor g0, std::vector<torch::Tensor> lanes, c10::optiona
 
 void sumsq(torch::Tensor g, torch::Tensor out) {
   req(g, torch::kFloat32, "g");
+  reqn(out, torch::kFloat32, 1, "out");
   check(mp_sumsq(g.data_ptr<float>(), g.numel(), out.data_ptr<float>(), cur_stream()), "sumsq");
 }
 
@@ -253,7 +282,11 @@ void adamw(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c
            c10::optional<torch::Tensor> sumsq_buf, double max_norm, double grad_scale, bool zero_grad) {
   req(p, torch::kFloat32, "p");
   req(g, torch::kFloat32, "g");
-  TORCH_CHECK(g.numel() == p.numel() && m.numel() == p.numel() && v.numel() == p.numel(), "bad adamw shapes");
+  reqn(m, torch::kFloat32, p.numel(), "m");
+  reqn(v, torch::kFloat32, p.numel(), "v");
+  if (w16.has_value()) reqn(*w16, torch::kBFloat16, p.numel(), "w16");
+  if (sumsq_buf.has_value()) reqn(*sumsq_buf, torch::kFloat32, 1, "sumsq_buf");
+  TORCH_CHECK(g.numel() == p.numel(), "bad adamw shapes");
   check(mp_adamw(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), mptr_or_null(w16),
                  p.numel(), n_decay, (float)lr, (float)b1, (float)b2, (float)eps, (float)wd, (int)step,
                  sumsq_buf.has_value() ? sumsq_buf->data_ptr<float>() : nullptr, (float)max_norm, (float)grad_scale,
@@ -263,11 +296,13 @@ void adamw(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c
 
 void cast_f32_bf16(torch::Tensor src, torch::Tensor dst) {
   req(src, torch::kFloat32, "src");
+  reqn(dst, torch::kBFloat16, src.numel(), "dst");
   check(mp_cast_f32_bf16(src.data_ptr<float>(), dst.data_ptr(), src.numel(), cur_stream()), "cast");
 }
 
 void act_fwd(torch::Tensor a, torch::Tensor g, int64_t act, double p, int64_t seed) {
   req(a, torch::kBFloat16, "a");
+  reqn(g, torch::kBFloat16, a.numel(), "g");
   check(mp_act_fwd(a.data_ptr(), g.data_ptr(), a.numel(), act, (float)p, (uint64_t)seed, cur_stream()), "act_fwd");
 }
 
@@ -276,6 +311,9 @@ void act_bwd(torch::Tensor dg, torch::Tensor a, torch::Tensor da, c10::optional<
   req(dg, torch::kBFloat16, "dg");
   const int cols = dg.size(-1);
   const int rows = dg.numel() / cols;
+  reqn(a, torch::kBFloat16, dg.numel(), "a");
+  reqn(da, torch::kBFloat16, dg.numel(), "da");
+  if (dbias.has_value()) reqn(*dbias, torch::kFloat32, cols, "dbias");
   const int64_t pe = dbias.has_value() ? mp_colsum_part_elems(rows, cols) : 0;
   torch::Tensor part;
   if (pe > 0) part = torch::empty({pe}, dg.options().dtype(torch::kFloat32));
@@ -301,17 +339,32 @@ void colsum(torch::Tensor x, torch::Tensor dbias) {
 
 void swiglu_fwd(torch::Tensor gu, torch::Tensor y) {
   const int F = y.size(-1);
+  req(y, torch::kBFloat16, "y");
+  reqn(gu, torch::kBFloat16, 2 * y.numel(), "gu");
+  TORCH_CHECK(gu.size(-1) == 2 * F, "swiglu_fwd: gu rows must be gate | up of 2 F columns");
   check(mp_swiglu_fwd(gu.data_ptr(), y.data_ptr(), y.numel() / F, F, cur_stream()), "swiglu_fwd");
 }
 
 void swiglu_bwd(torch::Tensor gu, torch::Tensor dy, torch::Tensor dgu) {
   const int F = dy.size(-1);
+  req(dy, torch::kBFloat16, "dy");
+  reqn(gu, torch::kBFloat16, 2 * dy.numel(), "gu");
+  reqn(dgu, torch::kBFloat16, 2 * dy.numel(), "dgu");
+  TORCH_CHECK(gu.size(-1) == 2 * F, "swiglu_bwd: gu rows must be gate | up of 2 F columns");
   check(mp_swiglu_bwd(gu.data_ptr(), dy.data_ptr(), dgu.data_ptr(), dy.numel() / F, F, cur_stream()), "swiglu_bwd");
 }
 
 void rope(torch::Tensor qkv, torch::Tensor cs, torch::Tensor sn, int64_t S, int64_t H, int64_t Hkv, int64_t Dh,
           int64_t pos_offset, bool inverse) {
-  const int T = qkv.numel() / ((H + 2 * Hkv) * Dh);
+  TORCH_CHECK(H >= 1 && Hkv >= 1 && Dh >= 8 && Dh % 8 == 0, "rope: bad head counts / head_dim");
+  const int64_t width = (H + 2 * Hkv) * Dh;
+  req(qkv, torch::kBFloat16, "qkv");
+  TORCH_CHECK(qkv.numel() % width == 0, "rope: qkv must hold whole [(H + 2 Hkv) Dh] rows");
+  const int T = qkv.numel() / width;
+  req(cs, torch::kFloat32, "cos");
+  req(sn, torch::kFloat32, "sin");
+  req_pos_table(cs, Dh / 2, T, S, pos_offset, "cos");
+  req_pos_table(sn, Dh / 2, T, S, pos_offset, "sin");
   check(mp_rope(qkv.data_ptr(), cs.data_ptr<float>(), sn.data_ptr<float>(), T, S, H, Hkv, Dh, pos_offset, inverse,
                 cur_stream()),
         "rope");

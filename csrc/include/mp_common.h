@@ -199,11 +199,14 @@ __device__ __forceinline__ float gelu_tanh(float x) {
 
 __device__ __forceinline__ float gelu_tanh_grad(float x) {
   const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-  const float x2 = x * x;
+  // x * x overflows beyond |x| ~ 1.8e19 (and 2 x beyond 1.7e38), where sg (1 - sg) is exactly
+  // 0: with x2 capped and sg (1 - sg) taken first the last term is 0 * finite = 0, not
+  // 0 * inf = NaN (u is saturated long before the cap)
+  const float x2 = fminf(x * x, 1e30f);
   const float u = k0 * (x + k1 * x2 * x);
   const float sg = sigmoid_fast(2.0f * u);  // = 0.5(1 + tanh u)
   // d/dx [x sg(2u)] = sg + x * 2 sg (1 - sg) * u'
-  return sg + 2.0f * x * sg * (1.0f - sg) * k0 * (1.0f + 3.0f * k1 * x2);
+  return sg + 2.0f * (sg * (1.0f - sg)) * x * k0 * (1.0f + 3.0f * k1 * x2);
 }
 
 // GELU and its derivative from one sigmoid: the forward GEMM epilogue saves the derivative

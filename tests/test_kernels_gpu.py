@@ -53,7 +53,7 @@ def test_norm_fwd_bwd(kind, D, branch):
         dw = torch.zeros(D, device=dev)
         db = torch.zeros(D, device=dev) if bias is not None else None
         ds, _ = ops.norm_bwd(mv(dy), s, mv(w), mean, rstd, kind=kind, dres=mv(dres), dw=dw, dbias=db)
-        outs.append((y, s, rstd, ds, dw, db))
+        outs.append((y, s, mean, rstd, ds, dw, db))
     for a, b in zip(*outs):
         if a is not None:
             close(b, a, atol=3e-2, rtol=3e-2)
