@@ -5,6 +5,9 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstdint>
+
 extern "C" {
 int mp_norm_fwd(int f32, int rms, const void* a, const void* b, const void* w, const void* bias, void* s_out, void* y,
                 float* mean, float* rstd, int rows, int D, float eps, float p, uint64_t seed, hipStream_t st);
@@ -370,24 +373,55 @@ void rope(torch::Tensor qkv, torch::Tensor cs, torch::Tensor sn, int64_t S, int6
         "rope");
 }
 
+// Argument checks of attn_fwd / attn_bwd, all before any launch: the kernels index raw
+// pointers by (B, S, heads, D) and the row strides, so a tensor of another dtype or a smaller
+// one would be read or written past its end.
+static void attn_check_dims(int64_t B, int64_t Sq, int64_t Sk, int64_t H, int64_t Hkv, int64_t D) {
+  TORCH_CHECK(B > 0 && Sq > 0 && Sk > 0 && H > 0 && Hkv > 0, "attn: B, Sq, Sk, H, Hkv must be positive (got ", B, ", ",
+              Sq, ", ", Sk, ", ", H, ", ", Hkv, ")");
+  TORCH_CHECK(H % Hkv == 0, "attn: H = ", H, " is not a multiple of Hkv = ", Hkv);
+  TORCH_CHECK(D > 0 && D % 8 == 0, "attn: head_dim ", D, " is not a positive multiple of 8");
+  TORCH_CHECK(B * std::max(Sq, Sk) <= INT32_MAX && std::max(H, Hkv) * D <= INT32_MAX, "attn: problem too large");
+}
+
+// a token-major [>= rows, >= cols] view of dtype `dt` with a unit inner stride
+static void attn_check_rows(const torch::Tensor& t, torch::ScalarType dt, int64_t rows, int64_t cols,
+                            const char* name) {
+  TORCH_CHECK(t.is_cuda(), "attn: ", name, " must be a GPU tensor");
+  TORCH_CHECK(t.scalar_type() == dt, "attn: ", name, " has dtype ", t.scalar_type(), ", q has ", dt,
+              " (q, k, v, o, dout, dq, dk, dv share one dtype)");
+  TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1, "attn: ", name, " must be a 2-D token-major view with unit inner stride");
+  TORCH_CHECK(t.size(0) >= rows && t.size(1) >= cols, "attn: ", name, " is [", t.size(0), ", ", t.size(1),
+              "], needs at least [", rows, ", ", cols, "]");
+  TORCH_CHECK(rows == 1 || t.stride(0) >= cols, "attn: ", name, " rows overlap (row stride ", t.stride(0), " < ", cols, ")");
+}
+
+// a contiguous f32 vector of at least n elements (lse, delta)
+static void attn_check_vec(const torch::Tensor& t, int64_t n, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.numel() >= n, "attn: ", name,
+              " must be a contiguous f32 GPU tensor of at least B*H*Sq = ", n, " elements");
+}
+
 // q/k/v/o are [B*S, stride] row views (token-major), heads at h*D inside a row.
 void attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o, torch::Tensor lse, int64_t B,
               int64_t Sq, int64_t Sk, int64_t H, int64_t Hkv, int64_t D, bool causal, double scale, double p,
               int64_t seed) {
-  req(lse, torch::kFloat32, "lse");
-  TORCH_CHECK(lse.numel() >= B * H * Sq, "lse too small");
-  TORCH_CHECK(q.stride(1) == 1 && k.stride(1) == 1 && v.stride(1) == 1 && o.stride(1) == 1, "attn: token-major rows");
-  if (q.scalar_type() == torch::kFloat32) {
+  attn_check_dims(B, Sq, Sk, H, Hkv, D);
+  const torch::ScalarType dt = q.scalar_type();
+  TORCH_CHECK(dt == torch::kBFloat16 || dt == torch::kFloat32, "attn: bf16 or f32");
+  attn_check_rows(q, dt, B * Sq, H * D, "q");
+  attn_check_rows(k, dt, B * Sk, Hkv * D, "k");
+  attn_check_rows(v, dt, B * Sk, Hkv * D, "v");
+  attn_check_rows(o, dt, B * Sq, H * D, "o");
+  attn_check_vec(lse, B * H * Sq, "lse");
+  if (dt == torch::kFloat32) {
     // f32 flash attention (attention_f32.hip): the reference-precision path
-    TORCH_CHECK(k.scalar_type() == torch::kFloat32 && v.scalar_type() == torch::kFloat32 &&
-                    o.scalar_type() == torch::kFloat32, "attn f32: q/k/v/o all f32");
     check(mp_attn_f32_fwd(q.data_ptr<float>(), k.data_ptr<float>(), v.data_ptr<float>(), o.data_ptr<float>(),
                           lse.data_ptr<float>(), B, Sq, Sk, H, Hkv, D, q.stride(0), k.stride(0), v.stride(0),
                           o.stride(0), causal, (float)scale, (float)p, (uint64_t)seed, cur_stream()),
           "attn_f32_fwd");
     return;
   }
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 && o.scalar_type() == torch::kBFloat16, "attn: bf16 or f32");
   check(mp_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), B, Sq, Sk, H, Hkv,
                     D, q.stride(0), k.stride(0), v.stride(0), o.stride(0), causal, (float)scale, (float)p,
                     (uint64_t)seed, cur_stream()),
@@ -398,11 +432,22 @@ void attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o
               torch::Tensor lse, torch::Tensor delta, torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
               int64_t B, int64_t Sq, int64_t Sk, int64_t H, int64_t Hkv, int64_t D, bool causal,
               double scale, double p, int64_t seed, c10::optional<torch::Tensor> dbias) {
+  attn_check_dims(B, Sq, Sk, H, Hkv, D);
+  const torch::ScalarType dt = q.scalar_type();
+  TORCH_CHECK(dt == torch::kBFloat16 || dt == torch::kFloat32, "attn: bf16 or f32");
+  attn_check_rows(q, dt, B * Sq, H * D, "q");
+  attn_check_rows(k, dt, B * Sk, Hkv * D, "k");
+  attn_check_rows(v, dt, B * Sk, Hkv * D, "v");
+  attn_check_rows(o, dt, B * Sq, H * D, "o");
+  attn_check_rows(dout, dt, B * Sq, H * D, "dout");
+  attn_check_rows(dq, dt, B * Sq, H * D, "dq");
+  attn_check_rows(dk, dt, B * Sk, Hkv * D, "dk");
+  attn_check_rows(dv, dt, B * Sk, Hkv * D, "dv");
+  attn_check_vec(lse, B * H * Sq, "lse");
+  attn_check_vec(delta, B * H * Sq, "delta");
   TORCH_CHECK(o.stride(0) == dout.stride(0), "o and dout must share a row stride");
-  if (q.scalar_type() == torch::kFloat32) {
+  if (dt == torch::kFloat32) {
     TORCH_CHECK(!dbias.has_value(), "attn_bwd f32: no fused bias sums");
-    for (const torch::Tensor* t : {&k, &v, &o, &dout, &dq, &dk, &dv})
-      TORCH_CHECK(t->scalar_type() == torch::kFloat32 && t->stride(1) == 1, "attn_bwd f32: f32 token-major rows");
     check(mp_attn_f32_bwd(q.data_ptr<float>(), k.data_ptr<float>(), v.data_ptr<float>(), o.data_ptr<float>(),
                           dout.data_ptr<float>(), lse.data_ptr<float>(), delta.data_ptr<float>(), dq.data_ptr<float>(),
                           dk.data_ptr<float>(), dv.data_ptr<float>(), B, Sq, Sk, H, Hkv, D, q.stride(0), k.stride(0),
@@ -414,7 +459,7 @@ void attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o
   // dbias: f32 [(H + 2 Hkv) D] QKV bias gradient, accumulated by the kernels (q | k | v)
   float* cs = nullptr;
   if (dbias.has_value()) {
-    TORCH_CHECK(dbias->scalar_type() == torch::kFloat32 && dbias->is_contiguous() &&
+    TORCH_CHECK(dbias->is_cuda() && dbias->scalar_type() == torch::kFloat32 && dbias->is_contiguous() &&
                     dbias->numel() == (H + 2 * Hkv) * D,
                 "attn_bwd: dbias must be a contiguous f32 [(H + 2 Hkv) D] tensor");
     cs = dbias->data_ptr<float>();
