@@ -1,6 +1,7 @@
 // Python bindings of the mipipe HIP kernels (torch tensors in, launches on the current
 // HIP stream).  Kernels live in csrc/kernels/*.hip behind plain C launchers so only
 // this file pays for the torch headers.  No hipify: written against HIP directly.
+#include <climits>
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
@@ -31,6 +32,7 @@ int mp_gemm_f32_ex(const float* A, const float* B, float* C, const float* bias, 
                    float alpha, int accumulate, float p_drop, uint64_t seed, int force_split, float* ws,
                    hipStream_t st);
 int64_t mp_gemm_f32_ws_elems(int M, int N, int K, int force_split);
+int mp_gemm_f32_plan(int M, int N, int K, int force_split, int* split, int* sk_grid, int* sk_chunk);
 int mp_lane_merge(float* g0, float* g1, float* g2, float* g3, int64_t n, float* sumsq, hipStream_t st);
 int mp_adamw(float* p, float* g, float* m, float* v, void* w16, int64_t n, int64_t n_decay, float lr, float b1,
              float b2, float eps, float wd, int step, const float* sumsq, float max_norm, float grad_scale,
@@ -514,17 +516,64 @@ int64_t attn_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cach
   return ns;
 }
 
+// ---- host-side argument checks of the GEMM bindings: every tensor a kernel will touch is
+// looked at before any launch, and the message names the argument
+bool aligned16(const torch::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
+
+// a 2-D operand of 16-byte row accesses: on `ref`'s GPU, dtype dt, unit inner stride, rows and
+// base 16-byte aligned (per = elements per 16 bytes)
+void gemm_operand(const char* fn, const char* name, const torch::Tensor& t, torch::ScalarType dt,
+                  const torch::Tensor& ref) {
+  TORCH_CHECK(t.is_cuda(), fn, ": ", name, " must be on the GPU");
+  TORCH_CHECK(t.get_device() == ref.get_device(), fn, ": ", name, " is on another device than A");
+  TORCH_CHECK(t.scalar_type() == dt, fn, ": ", name, " must be ", dt, ", got ", t.scalar_type());
+  TORCH_CHECK(t.dim() == 2, fn, ": ", name, " must be 2-D, got ", t.dim(), " dimensions");
+  TORCH_CHECK(t.size(0) > 0 && t.size(1) > 0, fn, ": ", name, " is empty");
+  TORCH_CHECK(t.stride(1) == 1, fn, ": ", name, " needs a unit inner stride");
+  const int64_t per = dt == torch::kFloat32 ? 4 : 8;
+  TORCH_CHECK(aligned16(t) && (t.size(0) == 1 || t.stride(0) % per == 0), fn, ": ", name,
+              " rows must be 16-byte aligned (base address and row stride)");
+}
+
+// the tensors of gemm / gemm2 against the epilogue that reads or writes them
+void gemm_args(const char* fn, const torch::Tensor& A, const torch::Tensor& B, const torch::Tensor& C,
+               const c10::optional<torch::Tensor>& bias, const c10::optional<torch::Tensor>& residual,
+               const c10::optional<torch::Tensor>& aux, bool transA, bool transB, int64_t epi, bool accum) {
+  TORCH_CHECK(A.is_cuda(), fn, ": A must be on the GPU");
+  gemm_operand(fn, "A", A, torch::kBFloat16, A);
+  gemm_operand(fn, "B", B, torch::kBFloat16, A);
+  TORCH_CHECK(!accum || C.scalar_type() == torch::kFloat32, fn, ": accumulate needs f32 C");
+  gemm_operand(fn, "C", C, accum ? torch::kFloat32 : torch::kBFloat16, A);
+  const int64_t M = C.size(0), N = C.size(1), K = transA ? A.size(0) : A.size(1);
+  TORCH_CHECK(M <= INT_MAX && N <= INT_MAX && K <= INT_MAX, fn, ": M, N, K must fit 32 bits");
+  TORCH_CHECK((transA ? A.size(1) : A.size(0)) == M, fn, ": A/M mismatch");
+  TORCH_CHECK((transB ? B.size(0) : B.size(1)) == K && (transB ? B.size(1) : B.size(0)) == N, fn, ": B mismatch");
+  TORCH_CHECK(epi >= 0 && epi <= 7, fn, ": epilogue ", epi, " outside 0..7");
+  const bool need_bias = epi >= 1 && epi <= 4, need_res = epi == 4 || epi == 5, need_aux = epi == 2 || epi == 3 || epi >= 6;
+  if (need_bias) {
+    TORCH_CHECK(bias.has_value(), fn, ": epilogue ", epi, " needs bias");
+    TORCH_CHECK(bias->is_cuda() && bias->get_device() == A.get_device(), fn, ": bias must be on A's GPU");
+    TORCH_CHECK(bias->scalar_type() == torch::kBFloat16, fn, ": bias must be bf16, got ", bias->scalar_type());
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N && aligned16(*bias), fn,
+                ": bias must be a contiguous 16-byte aligned [N] tensor, N = ", N, ", got ", bias->numel(), " elements");
+  }
+  const auto row_input = [&](const c10::optional<torch::Tensor>& t, const char* name) {
+    TORCH_CHECK(t.has_value(), fn, ": epilogue ", epi, " needs ", name);
+    gemm_operand(fn, name, *t, torch::kBFloat16, A);
+    TORCH_CHECK(t->size(0) == M && t->size(1) == N, fn, ": ", name, " must be [M, N] = [", M, ", ", N, "]");
+  };
+  if (need_res) row_input(residual, "residual");
+  if (need_aux) row_input(aux, "aux");
+}
+
 // C[M,N] (+)= alpha * op(A) @ op(B) with fused epilogue.
 //   A: [M,K] row-major (transA=0) or [K,M] (transA=1); B: [N,K] (transB=0, "NT") or [K,N] (transB=1)
 void gemm(torch::Tensor A, torch::Tensor B, torch::Tensor C, c10::optional<torch::Tensor> bias,
           c10::optional<torch::Tensor> residual, c10::optional<torch::Tensor> aux, bool transA, bool transB,
           int64_t epilogue, bool accum, double alpha) {
+  gemm_args("gemm", A, B, C, bias, residual, aux, transA, transB, epilogue, accum);
   const int M = C.size(0), N = C.size(1);
   const int K = transA ? A.size(0) : A.size(1);
-  TORCH_CHECK((transA ? A.size(1) : A.size(0)) == M, "gemm: A/M mismatch");
-  TORCH_CHECK((transB ? B.size(0) : B.size(1)) == K && (transB ? B.size(1) : B.size(0)) == N, "gemm: B mismatch");
-  TORCH_CHECK(A.stride(1) == 1 && B.stride(1) == 1 && C.stride(1) == 1, "gemm: inner dims must be contiguous");
-  TORCH_CHECK(!accum || C.scalar_type() == torch::kFloat32, "gemm: accumulate needs f32 C");
   check(mp_gemm(A.data_ptr(), B.data_ptr(), C.data_ptr(), ptr_or_null(bias), ptr_or_null(residual), mptr_or_null(aux),
                 M, N, K, A.stride(0), B.stride(0), C.stride(0), residual.has_value() ? residual->stride(0) : 0,
                 aux.has_value() ? aux->stride(0) : 0, transA, transB, epilogue, accum, (float)alpha, cur_stream()),
@@ -539,15 +588,20 @@ int64_t gemm2(torch::Tensor A, torch::Tensor B, torch::Tensor C, c10::optional<t
               c10::optional<torch::Tensor> residual, c10::optional<torch::Tensor> aux, bool transA, bool transB,
               int64_t epilogue, bool accum, double alpha, int64_t force_cfg, c10::optional<torch::Tensor> colsum,
               double p_drop, int64_t seed) {
+  gemm_args("gemm2", A, B, C, bias, residual, aux, transA, transB, epilogue, accum);
   const int M = C.size(0), N = C.size(1);
   const int K = transA ? A.size(0) : A.size(1);
-  TORCH_CHECK((transA ? A.size(1) : A.size(0)) == M, "gemm2: A/M mismatch");
-  TORCH_CHECK((transB ? B.size(0) : B.size(1)) == K && (transB ? B.size(1) : B.size(0)) == N, "gemm2: B mismatch");
-  TORCH_CHECK(A.stride(1) == 1 && B.stride(1) == 1 && C.stride(1) == 1, "gemm2: inner dims must be contiguous");
-  TORCH_CHECK(!accum || C.scalar_type() == torch::kFloat32, "gemm2: accumulate needs f32 C");
-  TORCH_CHECK(!colsum.has_value() || (colsum->scalar_type() == torch::kFloat32 && colsum->is_contiguous() &&
+  TORCH_CHECK(!colsum.has_value() || (colsum->is_cuda() && colsum->get_device() == A.get_device() &&
+                                      colsum->scalar_type() == torch::kFloat32 && colsum->is_contiguous() &&
                                       colsum->numel() >= N),
-              "gemm2: colsum must be a contiguous f32 [N] tensor");
+              "gemm2: colsum must be a contiguous f32 [N] tensor on A's GPU");
+  TORCH_CHECK(p_drop >= 0.0 && p_drop < 1.0, "gemm2: p_drop ", p_drop, " outside [0, 1)");
+  if (p_drop > 0.0) {
+    TORCH_CHECK(epilogue == 2 || epilogue == 3 || epilogue == 6 || epilogue == 7, "gemm2: p_drop with epilogue ",
+                epilogue, ", which takes no dropout");
+    // the mask index is row * ldc + column: act_fwd / act_bwd regenerate it for a contiguous output
+    TORCH_CHECK(C.is_contiguous(), "gemm2: p_drop needs a contiguous C");
+  }
   // split-K slabs (plain stores + one reduce pass instead of f32 atomics)
   // split-K slabs (plain stores + one reduce pass instead of f32 atomics), or the stream-K
   // engine's flags + partial tiles: from the caching allocator on the current stream (graph
@@ -592,12 +646,10 @@ void gemm_tt_grouped(std::vector<torch::Tensor> dy, std::vector<torch::Tensor> x
   int M[8], N[8], K[8];
   int64_t lda[8], ldb[8], ldc[8];
   for (int i = 0; i < n; ++i) {
-    TORCH_CHECK(dy[i].is_cuda() && dy[i].scalar_type() == torch::kBFloat16 && x[i].scalar_type() == torch::kBFloat16 &&
-                    C[i].scalar_type() == torch::kFloat32,
-                "gemm_tt_grouped: bf16 dy/x, f32 C");
-    TORCH_CHECK(dy[i].dim() == 2 && x[i].dim() == 2 && C[i].dim() == 2 && dy[i].stride(1) == 1 &&
-                    x[i].stride(1) == 1 && C[i].stride(1) == 1,
-                "gemm_tt_grouped: 2-D, unit inner stride");
+    TORCH_CHECK(dy[0].is_cuda(), "gemm_tt_grouped: dy must be on the GPU");
+    gemm_operand("gemm_tt_grouped", "dy", dy[i], torch::kBFloat16, dy[0]);
+    gemm_operand("gemm_tt_grouped", "x", x[i], torch::kBFloat16, dy[0]);
+    gemm_operand("gemm_tt_grouped", "C", C[i], torch::kFloat32, dy[0]);
     TORCH_CHECK(dy[i].size(0) == x[i].size(0) && C[i].size(0) == dy[i].size(1) && C[i].size(1) == x[i].size(1),
                 "gemm_tt_grouped: shape mismatch");
     A[i] = dy[i].data_ptr();
@@ -614,7 +666,10 @@ void gemm_tt_grouped(std::vector<torch::Tensor> dy, std::vector<torch::Tensor> x
 }
 
 void transpose(torch::Tensor in, torch::Tensor out) {
+  TORCH_CHECK(in.is_cuda() && out.is_cuda() && in.get_device() == out.get_device(), "transpose: in and out must be on one GPU");
+  TORCH_CHECK(in.scalar_type() == torch::kBFloat16 && out.scalar_type() == torch::kBFloat16, "transpose: in and out must be bf16");
   TORCH_CHECK(in.dim() == 2 && out.dim() == 2 && in.stride(1) == 1 && out.stride(1) == 1, "transpose: 2-D rows");
+  TORCH_CHECK(in.size(0) > 0 && in.size(1) > 0, "transpose: in is empty");
   TORCH_CHECK(out.size(0) == in.size(1) && out.size(1) == in.size(0), "transpose: shape");
   check(mp_transpose(in.data_ptr(), out.data_ptr(), in.size(0), in.size(1), in.stride(0), out.stride(0),
                      cur_stream()),
@@ -690,13 +745,28 @@ namespace mipipe_runtime {
 void register_runner(pybind11::module& m);
 }
 
+// the f32 GEMM operands: on one GPU, f32, 2-D, non-empty
+void gemm_f32_args(const char* fn, const torch::Tensor& A, const torch::Tensor& B, const torch::Tensor& C,
+                   const c10::optional<torch::Tensor>& bias) {
+  const torch::Tensor* ts[3] = {&A, &B, &C};
+  const char* names[3] = {"A", "B", "C"};
+  for (int i = 0; i < 3; ++i) {
+    TORCH_CHECK(ts[i]->is_cuda(), fn, ": ", names[i], " must be on the GPU");
+    TORCH_CHECK(ts[i]->get_device() == A.get_device(), fn, ": ", names[i], " is on another device than A");
+    TORCH_CHECK(ts[i]->scalar_type() == torch::kFloat32, fn, ": ", names[i], " must be f32, got ", ts[i]->scalar_type());
+    TORCH_CHECK(ts[i]->dim() == 2, fn, ": ", names[i], " must be 2-D, got ", ts[i]->dim(), " dimensions");
+    TORCH_CHECK(ts[i]->size(0) > 0 && ts[i]->size(1) > 0, fn, ": ", names[i], " is empty");
+  }
+  if (bias.has_value())
+    TORCH_CHECK(bias->is_cuda() && bias->get_device() == A.get_device() && bias->scalar_type() == torch::kFloat32, fn,
+                ": bias must be an f32 tensor on A's GPU");
+}
+
 // f32 MFMA GEMM: C (+)= alpha * A @ B (+ bias); A [M,K], B [K,N] 2-D views with either inner
 // stride 1; returns 1 if done, 0 if the layout is not supported (caller falls back)
 int64_t gemm_f32(torch::Tensor A, torch::Tensor B, torch::Tensor C, c10::optional<torch::Tensor> bias, double alpha,
                  bool accumulate) {
-  TORCH_CHECK(A.scalar_type() == torch::kFloat32 && B.scalar_type() == torch::kFloat32 &&
-                  C.scalar_type() == torch::kFloat32, "gemm_f32: f32 tensors");
-  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && C.dim() == 2, "gemm_f32: 2-D");
+  gemm_f32_args("gemm_f32", A, B, C, bias);
   const int M = A.size(0), K = A.size(1), N = B.size(1);
   TORCH_CHECK(B.size(0) == K && C.size(0) == M && C.size(1) == N, "gemm_f32: shape mismatch");
   if (C.stride(1) != 1) return 0;
@@ -725,10 +795,10 @@ int64_t gemm_f32(torch::Tensor A, torch::Tensor B, torch::Tensor C, c10::optiona
 int64_t gemm_f32_ex(torch::Tensor A, torch::Tensor B, torch::Tensor C, c10::optional<torch::Tensor> bias,
                     c10::optional<torch::Tensor> R, c10::optional<torch::Tensor> X, int64_t epi, double alpha,
                     bool accumulate, double p_drop, int64_t seed, int64_t force_ks) {
-  TORCH_CHECK(A.scalar_type() == torch::kFloat32 && B.scalar_type() == torch::kFloat32 &&
-                  C.scalar_type() == torch::kFloat32, "gemm_f32_ex: f32 tensors");
-  TORCH_CHECK(A.is_cuda() && B.is_cuda() && C.is_cuda(), "gemm_f32_ex: GPU tensors");
-  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && C.dim() == 2, "gemm_f32_ex: 2-D");
+  gemm_f32_args("gemm_f32_ex", A, B, C, bias);
+  TORCH_CHECK(epi >= 0 && epi <= 5, "gemm_f32_ex: epi ", epi, " outside 0..5");
+  TORCH_CHECK(p_drop >= 0.0 && p_drop < 1.0, "gemm_f32_ex: p_drop ", p_drop, " outside [0, 1)");
+  TORCH_CHECK(p_drop == 0.0 || epi == 2 || epi == 5, "gemm_f32_ex: p_drop with epi ", epi, ", which takes no dropout");
   const int M = A.size(0), K = A.size(1), N = B.size(1);
   TORCH_CHECK(B.size(0) == K && C.size(0) == M && C.size(1) == N, "gemm_f32_ex: shape mismatch");
   if (C.stride(1) != 1) return 0;
@@ -744,13 +814,15 @@ int64_t gemm_f32_ex(torch::Tensor A, torch::Tensor B, torch::Tensor C, c10::opti
   TORCH_CHECK(!need_bias || (bias.has_value() && bias->is_contiguous() && bias->numel() == N), "gemm_f32_ex: bias [N]");
   int64_t ldr = 0, ldx = 0;
   if (need_r) {
-    TORCH_CHECK(R.has_value() && R->scalar_type() == torch::kFloat32 && R->dim() == 2 && R->stride(1) == 1 &&
-                    R->size(0) == M && R->size(1) == N, "gemm_f32_ex: R [M,N] f32 rows");
+    TORCH_CHECK(R.has_value() && R->is_cuda() && R->get_device() == A.get_device() &&
+                    R->scalar_type() == torch::kFloat32 && R->dim() == 2 && R->stride(1) == 1 &&
+                    R->size(0) == M && R->size(1) == N, "gemm_f32_ex: R must be [M,N] f32 rows on A's GPU");
     ldr = R->stride(0);
   }
   if (need_x) {
-    TORCH_CHECK(X.has_value() && X->scalar_type() == torch::kFloat32 && X->dim() == 2 && X->stride(1) == 1 &&
-                    X->size(0) == M && X->size(1) == N, "gemm_f32_ex: X [M,N] f32 rows");
+    TORCH_CHECK(X.has_value() && X->is_cuda() && X->get_device() == A.get_device() &&
+                    X->scalar_type() == torch::kFloat32 && X->dim() == 2 && X->stride(1) == 1 &&
+                    X->size(0) == M && X->size(1) == N, "gemm_f32_ex: X must be [M,N] f32 rows on A's GPU");
     ldx = X->stride(0);
   }
   // split-K slabs from the caching allocator (inside a graph capture: the graph's pool)
@@ -822,5 +894,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     const int cfg = mp_gemm2_plan((int)M, (int)N, (int)K, transA, transB, accum, (int)force_cfg, &split);
     return std::make_tuple(cfg, split);
   }, "engine config + split-K factor the v2 GEMM picks (14: stream-K gemm7)");
+  m.def("gemm_f32_plan", [](int64_t M, int64_t N, int64_t K, int64_t force_ks) {
+    int split = 1, sk_grid = 0, sk_chunk = 0;
+    const int big = mp_gemm_f32_plan((int)M, (int)N, (int)K, (int)force_ks, &split, &sk_grid, &sk_chunk);
+    return std::make_tuple(big != 0, split, sk_grid, sk_chunk);
+  }, "what gemm_f32_ex will run: (128x128 engine, split-K factor, stream-K workgroups, K-tile pairs per workgroup)");
   m.def("gemm2_has_probe_engines", []() { return mp_gemm2_has_probe_engines() != 0; });
 }

@@ -218,6 +218,10 @@ __device__ __forceinline__ void gelu_tanh_and_grad(float x, float& g, float& d) 
   const float sg = sigmoid_fast(2.0f * u);
   g = x * sg;
   d = sg + 2.0f * x * sg * (1.0f - sg) * k0 * (1.0f + 3.0f * k1 * x2);
+  // beyond |x| ~ 1.8e19 x2 is inf (and 2 x overflows beyond 1.7e38) while sg (1 - sg) is
+  // exactly 0: the second term is 0 * inf = NaN there, and the derivative is sg itself.
+  // Below that the value above is kept bit for bit.
+  if (!(fabsf(x) < 1.0e18f)) d = sg;
 }
 
 // max of three as ONE v_max3_f32.  fmaxf makes the compiler canonicalise each input first

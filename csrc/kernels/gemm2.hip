@@ -1498,6 +1498,10 @@ static int launch8(const void* A, const void* B, void* C, const void* bias, cons
   constexpr int LDS_MAIN = 0x10000 + 256 * 128 + 192 * 128;   // buffer 1 ends at 120 KiB
   constexpr int EPI_BYTES = 128 * (192 + 4) * 4;
   constexpr int LDS = LDS_MAIN > EPI_BYTES ? LDS_MAIN : EPI_BYTES;
+  // the kernel addresses a tile's rows through 32-bit buffer offsets (resource size, voa / vob
+  // + u * rsa / rsb: up to 255 rows x ld x 2 bytes): beyond 2^31 they wrap and the hardware
+  // returns zeros for rows it should load, so such strides go back to the caller (v1 takes them)
+  if ((255 * lda + K) * 2 >= (int64_t)1 << 31 || (255 * ldb + K) * 2 >= (int64_t)1 << 31) return -1;
   auto kern = gemm8_kernel<EPI, ACC, PGR>;
   static bool attr = false;
   if (!attr) {

@@ -697,6 +697,16 @@ extern "C" int64_t mp_gemm_f32_ws_elems(int M, int N, int K, int force_split) {
   return pl.split > 1 ? (int64_t)pl.split * M * N : 0;
 }
 
+// what mp_gemm_f32_ex will run for this problem: returns 1 for the 128x128 engine; *split = the
+// split-K factor, *sk_grid / *sk_chunk = stream-K workgroups and K-tile pairs each (0: off)
+extern "C" int mp_gemm_f32_plan(int M, int N, int K, int force_split, int* split, int* sk_grid, int* sk_chunk) {
+  const gf32::Plan pl = gf32::plan(M, N, K, force_split);
+  *split = pl.split;
+  *sk_grid = pl.sk_grid;
+  *sk_chunk = pl.sk_chunk;
+  return pl.big ? 1 : 0;
+}
+
 // epi: 0 none, 1 bias, 2 bias+ReLU (+dropout p_drop; pre-activation -> X), 3 residual,
 // 4 bias+residual, 5 dReLU (pre-activation in R) x dropout mask.  Dropout element index =
 // row * N + col (identical in the forward and the backward).  ws: the split-K workspace
