@@ -54,6 +54,14 @@ int mp_attn_bwd(const void* q, const void* k, const void* v, const void* o, cons
                 int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int64_t dq_stride,
                 int64_t dk_stride, int64_t dv_stride, int causal, float scale, float p_drop, uint64_t seed,
                 float* csq, float* csk, float* csv, hipStream_t st);
+int mp_attn_doc_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int* doc_start, int B,
+                    int S, int H, int Hkv, int D, int64_t qs, int64_t ks, int64_t vs, int64_t os, float scale,
+                    hipStream_t st);
+int mp_attn_doc_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                    float* delta, void* dq, void* dk, void* dv, const int* doc_start, const int* doc_end, int B, int S,
+                    int H, int Hkv, int D, int64_t qs, int64_t ks, int64_t vs, int64_t os, int64_t dqs, int64_t dks,
+                    int64_t dvs, float scale, hipStream_t st);
+int mp_doc_bounds(const int64_t* tokens, int64_t eos, int* doc_start, int* doc_end, int B, int S, hipStream_t st);
 int mp_attn_decode(const void* q, const void* k, const void* v, const int* lens, void* o, float* ws, int B, int H,
                    int Hkv, int D, int Smax, int max_len, int64_t q_stride, int64_t k_bs, int64_t k_ts, int64_t v_bs,
                    int64_t v_ts, int64_t o_stride, float scale, int splits, hipStream_t st);
@@ -474,6 +482,87 @@ void attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o
         "attn_bwd");
 }
 
+// Document-masked causal attention (attention_doc.hip).  All checks before any launch.
+static void attn_doc_check_common(const torch::Tensor& q, int64_t B, int64_t S, int64_t H, int64_t Hkv, int64_t D,
+                                  bool causal, double p) {
+  attn_check_dims(B, S, S, H, Hkv, D);
+  TORCH_CHECK(causal, "attn_doc: the document mask is causal only");
+  TORCH_CHECK(p == 0.0, "attn_doc: no dropout (p_drop = ", p, ")");
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16, "attn_doc: bf16 tensors only (q has ", q.scalar_type(), ")");
+  TORCH_CHECK(D == 64 || D == 128, "attn_doc: head_dim ", D, " is not supported (64 or 128)");
+}
+
+// 16-byte rows (the kernels move 8 bf16 at a time) whose offsets inside one sequence fit 32 bits
+static void attn_doc_check_rows(const torch::Tensor& t, int64_t B, int64_t S, int64_t cols, const char* name) {
+  attn_check_rows(t, torch::kBFloat16, B * S, cols, name);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 && (B * S == 1 || t.stride(0) % 8 == 0),
+              "attn_doc: ", name, " rows must be 16-byte aligned (row stride ", t.stride(0), ")");
+  TORCH_CHECK((S + 128) * t.stride(0) * 2 < (int64_t(1) << 31), "attn_doc: ", name, " row stride ", t.stride(0),
+              " is too large for S = ", S);
+}
+
+static void attn_doc_check_bounds(const torch::Tensor& t, const torch::Tensor& q, int64_t n, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == q.device(), "attn_doc: ", name, " must be on q's device");
+  TORCH_CHECK(t.scalar_type() == torch::kInt32, "attn_doc: ", name, " must be int32 (got ", t.scalar_type(), ")");
+  TORCH_CHECK(t.is_contiguous(), "attn_doc: ", name, " must be contiguous");
+  TORCH_CHECK(t.numel() == n, "attn_doc: ", name, " has ", t.numel(), " entries, needs B*S = ", n);
+}
+
+void attn_doc_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o, torch::Tensor lse,
+                  torch::Tensor doc_start, int64_t B, int64_t S, int64_t H, int64_t Hkv, int64_t D, bool causal,
+                  double scale, double p) {
+  attn_doc_check_common(q, B, S, H, Hkv, D, causal, p);
+  attn_doc_check_rows(q, B, S, H * D, "q");
+  attn_doc_check_rows(k, B, S, Hkv * D, "k");
+  attn_doc_check_rows(v, B, S, Hkv * D, "v");
+  attn_doc_check_rows(o, B, S, H * D, "o");
+  attn_check_vec(lse, B * H * S, "lse");
+  attn_doc_check_bounds(doc_start, q, B * S, "doc_start");
+  check(mp_attn_doc_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
+                        doc_start.data_ptr<int>(), B, S, H, Hkv, D, q.stride(0), k.stride(0), v.stride(0), o.stride(0),
+                        (float)scale, cur_stream()),
+        "attn_doc_fwd");
+}
+
+void attn_doc_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o, torch::Tensor dout,
+                  torch::Tensor lse, torch::Tensor delta, torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
+                  torch::Tensor doc_start, torch::Tensor doc_end, int64_t B, int64_t S, int64_t H, int64_t Hkv,
+                  int64_t D, bool causal, double scale, double p) {
+  attn_doc_check_common(q, B, S, H, Hkv, D, causal, p);
+  attn_doc_check_rows(q, B, S, H * D, "q");
+  attn_doc_check_rows(k, B, S, Hkv * D, "k");
+  attn_doc_check_rows(v, B, S, Hkv * D, "v");
+  attn_doc_check_rows(o, B, S, H * D, "o");
+  attn_doc_check_rows(dout, B, S, H * D, "dout");
+  attn_doc_check_rows(dq, B, S, H * D, "dq");
+  attn_doc_check_rows(dk, B, S, Hkv * D, "dk");
+  attn_doc_check_rows(dv, B, S, Hkv * D, "dv");
+  attn_check_vec(lse, B * H * S, "lse");
+  attn_check_vec(delta, B * H * S, "delta");
+  TORCH_CHECK(o.stride(0) == dout.stride(0), "o and dout must share a row stride");
+  attn_doc_check_bounds(doc_start, q, B * S, "doc_start");
+  attn_doc_check_bounds(doc_end, q, B * S, "doc_end");
+  check(mp_attn_doc_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(),
+                        delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), doc_start.data_ptr<int>(),
+                        doc_end.data_ptr<int>(), B, S, H, Hkv, D, q.stride(0), k.stride(0), v.stride(0), o.stride(0),
+                        dq.stride(0), dk.stride(0), dv.stride(0), (float)scale, cur_stream()),
+        "attn_doc_bwd");
+}
+
+// tokens: contiguous int64 [B, S] on the GPU -> (doc_start, doc_end), int32 [B*S]; no host sync
+std::vector<torch::Tensor> doc_bounds(torch::Tensor tokens, int64_t eos) {
+  TORCH_CHECK(tokens.is_cuda() && tokens.scalar_type() == torch::kInt64 && tokens.dim() == 2 && tokens.is_contiguous(),
+              "doc_bounds: tokens must be a contiguous int64 [B, S] GPU tensor");
+  const int64_t B = tokens.size(0), S = tokens.size(1);
+  TORCH_CHECK(B > 0 && S > 0 && B * S <= INT32_MAX, "doc_bounds: bad shape [", B, ", ", S, "]");
+  auto opt = torch::TensorOptions().dtype(torch::kInt32).device(tokens.device());
+  torch::Tensor ds = torch::empty({B * S}, opt), de = torch::empty({B * S}, opt);
+  check(mp_doc_bounds(tokens.data_ptr<int64_t>(), eos, ds.data_ptr<int>(), de.data_ptr<int>(), (int)B, (int)S,
+                      cur_stream()),
+        "doc_bounds");
+  return {ds, de};
+}
+
 // Decode attention (attention_decode.hip): one query row per sequence against its KV cache.
 // q/o: [B, H*D] row views; k_cache/v_cache: [B, Smax, Hkv*D] views with unit inner stride;
 // lens: int32 [B] on the device (valid keys per sequence); max_len >= max(lens) sizes the
@@ -867,6 +956,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope", &rope);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
+  m.def("attn_doc_fwd", &attn_doc_fwd);
+  m.def("attn_doc_bwd", &attn_doc_bwd);
+  m.def("doc_bounds", &doc_bounds);
   m.def("attn_decode", &attn_decode, pybind11::arg("q"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
         pybind11::arg("lens"), pybind11::arg("o"), pybind11::arg("H"), pybind11::arg("Hkv"), pybind11::arg("D"),
         pybind11::arg("max_len"), pybind11::arg("scale"), pybind11::arg("splits") = 0);

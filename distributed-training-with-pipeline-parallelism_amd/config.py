@@ -50,6 +50,9 @@ class TrainSection:
     graphs: Optional[bool] = None       # HIP-graph replay + native stage runner (None: on for GPU)
     seed: int = 0
     data: str = "synthetic"             # synthetic | pattern[:K] (learnable permutation walk) | path to a uint16/int32 token file (memory-mapped)
+    # packed documents: the end-of-text token id.  Set: attention stays inside each document of a
+    # window (ops.doc_bounds + PipelineTrainer(doc_mask=True)); None: plain causal attention
+    doc_eos: Optional[int] = None
     log_every: int = 10
     metrics_file: Optional[str] = None  # JSONL, one record per logged step
     ckpt_dir: Optional[str] = None

@@ -514,11 +514,27 @@ class PipelineTrainer:
                  recompute: bool = False, profile: bool = False, seed: int = 0, style: str = "loop",
                  mesh: Optional[Mesh] = None, layer_ranges=None, dtype=torch.bfloat16,
                  split_head: Optional[bool] = None, head_align: Optional[int] = None, graphs: bool = False,
-                 adam_eps: float = 1e-8, head_max_lag: Optional[int] = None):
+                 adam_eps: float = 1e-8, head_max_lag: Optional[int] = None, doc_mask: bool = False):
         """``head_max_lag``: cap on the distributed head's lag (extra warmup forwards; 0 = the
         schedule's own depth, e.g. 1F1B's P - s).  Whatever the cap, the lag is bounded by
-        the HBM plan (``self.mem_bound``)."""
+        the HBM plan (``self.mem_bound``).
+
+        ``doc_mask``: packed-document training.  Attention stays inside each document of a
+        row; every ``train_step`` / ``capture_graphs`` call then takes ``docs``, the
+        (doc_start, doc_end) pair of ``ops.doc_bounds`` for the whole batch.  Fixed at
+        construction because the captured graphs differ."""
         self.cfg = cfg
+        self.doc_mask = bool(doc_mask)
+        if self.doc_mask:
+            on_gpu = (torch.device(device).type == "cuda") if device is not None else torch.cuda.is_available()
+            if cfg.cross_attn or not cfg.causal:
+                raise ValueError("doc_mask: the document mask needs a causal pre-norm decoder")
+            if cfg.dropout > 0:
+                raise ValueError(f"doc_mask: the document-masked attention has no dropout (dropout = {cfg.dropout})")
+            if on_gpu and dtype != torch.bfloat16:
+                raise ValueError(f"doc_mask: the document-masked kernels are bf16 only on the GPU (dtype = {dtype})")
+            if on_gpu and cfg.head_dim not in (64, 128):
+                raise ValueError(f"doc_mask: head_dim {cfg.head_dim} is not supported on the GPU (64 or 128)")
         # schedule="auto": the best head-aware plan (pick_schedule; 1F1B at PP = 1)
         self.schedule_choice = None
         if str(schedule).lower() == "auto":
@@ -637,7 +653,8 @@ class PipelineTrainer:
                                 arena_multiple=8 * self.mesh.dp if self.dp_zero else 8)
             egroup = self.mesh.embed_group if (tied_pp and (s == 0 or s == num_stages - 1)) else None
             self.stages.append(NativeStage(model, mbs, seq_len, dp_group=self.mesh.dp_group, embed_group=egroup,
-                                           seed=seed + 1000 * self.mesh.dp_rank, graphs=graphs))
+                                           seed=seed + 1000 * self.mesh.dp_rank, graphs=graphs,
+                                           doc_mask_mbs=n_microbatches if self.doc_mask else 0))
         p2p = P2P(self.mesh.pp_group, self.mesh.pipe_ranks, self.device, ctrl_group=self.mesh.ctrl_group)
         # every collective of the step (DP all-reduce, head reduction, clip norm, losses)
         self.coll = Collectives(self.mesh, self.device, pipe_engine=p2p.engine, embed=tied_pp)
@@ -777,10 +794,33 @@ class PipelineTrainer:
     def num_params_local(self) -> int:
         return sum(st.arena.numel for st in self.stages)
 
+    def _set_docs(self, docs) -> None:
+        """Check the step's ``docs`` against the trainer's mode and copy them into every local
+        stage's persistent buffers (on the compute stream, before the pipeline program)."""
+        if not self.doc_mask:
+            if docs is not None:
+                raise ValueError("docs given, but the trainer was built with doc_mask=False")
+            return
+        if docs is None:
+            raise ValueError("doc_mask=True: every rank passes docs=(doc_start, doc_end) for the whole batch")
+        n = self.m * self.mbs * self.S
+        ds, de = docs
+        for name, t in (("doc_start", ds), ("doc_end", de)):
+            if t.dtype != torch.int32 or t.numel() != n:
+                raise ValueError(f"docs: {name} must be int32 with m*mbs*S = {n} entries "
+                                 f"(got {t.dtype}, {tuple(t.shape)})")
+        ds = ds.reshape(-1).to(self.device, non_blocking=True)
+        de = de.reshape(-1).to(self.device, non_blocking=True)
+        for st in self.stages:
+            st.set_docs(ds, de)
+
     def train_step(self, tokens: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None,
-                   lr: Optional[float] = None) -> Optional[torch.Tensor]:
+                   lr: Optional[float] = None, docs=None) -> Optional[torch.Tensor]:
         """tokens/targets: [m*mbs, S] int64 (tokens needed on the first stage's rank,
-        targets on the last).  Returns the mean loss tensor on the last-stage rank."""
+        targets on the last).  Returns the mean loss tensor on the last-stage rank.
+        ``docs``: (doc_start, doc_end) of the whole batch, int32 [m*mbs*S] each, on every
+        rank when the trainer was built with ``doc_mask=True`` (and only then)."""
+        self._set_docs(docs)
         inputs = None
         if self.is_first:
             inputs = [(c,) for c in torch.tensor_split(tokens, self.m, dim=0)]
@@ -864,10 +904,13 @@ class PipelineTrainer:
                 "\n".join(f"[comm audit]   {e}" for e in tail)
         return out
 
-    def capture_graphs(self, tokens: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None) -> None:
+    def capture_graphs(self, tokens: Optional[torch.Tensor] = None, targets: Optional[torch.Tensor] = None,
+                       docs=None) -> None:
         """Setup, not training: run the pipeline program twice without an optimizer step
         (eager lazy-init, then HIP-graph capture of every per-microbatch action) and
-        discard the gradients.  Later ``train_step`` calls replay the graphs."""
+        discard the gradients.  Later ``train_step`` calls replay the graphs.  ``docs``: as
+        in ``train_step``."""
+        self._set_docs(docs)
         if not any(st.graphs is not None for st in self.stages):
             return
         inputs = [(c,) for c in torch.tensor_split(tokens, self.m, dim=0)] if self.is_first else None

@@ -301,6 +301,9 @@ class MBContext:
         self.seed = seed
         self.layers: Dict[int, dict] = {}
         self.misc: dict = {}
+        # (doc_start, doc_end) int32 [B*S] of a packed-document microbatch, or None: read by
+        # every block's attention forward and backward (ops.attn_fwd's document mask)
+        self.docs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
 
 
 # MIPIPE_FUSE_QKV_BIAS=1: the attention backward kernels sum the QKV bias gradient
@@ -460,7 +463,7 @@ class Block:
         return self.A.g(self.P + n) if self.A.has(self.P + n) else None
 
     # ------------------------------------------------------------------ pre-norm
-    def _attn_fwd(self, h, B, S, st, seed):
+    def _attn_fwd(self, h, B, S, st, seed, docs=None):
         cfg = self.cfg
         H, KV, Dh = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
         qkv, _ = ops.linear(h, self.w("attn.wqkv.weight"), self.wb("attn.wqkv.bias"))
@@ -469,7 +472,8 @@ class Block:
         q, k, v = qkv[:, : H * Dh], qkv[:, H * Dh:(H + KV) * Dh], qkv[:, (H + KV) * Dh:]
         o = torch.empty(h.shape[0], H * Dh, device=h.device, dtype=h.dtype)
         lse = torch.empty(B * H * S, device=h.device, dtype=torch.float32)
-        ops.attn_fwd(q, k, v, o, lse, B, S, S, H, KV, Dh, cfg.causal, p_drop=cfg.dropout, seed=seed)
+        ops.attn_fwd(q, k, v, o, lse, B, S, S, H, KV, Dh, cfg.causal, p_drop=cfg.dropout, seed=seed,
+                     doc_start=docs[0] if docs is not None else None)
         st["qkv"], st["o"], st["lse"] = qkv, o, lse
         return o
 
@@ -478,12 +482,14 @@ class Block:
         st: dict = {}
         sd = _seed(ctx.seed, self.i)
         if cfg.cross_attn:
+            if ctx.docs is not None:
+                raise ValueError("the document mask needs a causal pre-norm decoder block")
             y = self._ref_forward(x, B, S, st, sd)
         else:
             kind = cfg.norm
             h1, _, mu1, rs1 = ops.norm_fwd(x, self.w("attn_norm.weight"), self.wb("attn_norm.bias"), kind=kind,
                                            eps=cfg.norm_eps)
-            o = self._attn_fwd(h1, B, S, st, _seed(sd, 1))
+            o = self._attn_fwd(h1, B, S, st, _seed(sd, 1), ctx.docs)
             x2, _ = ops.linear(o, self.w("attn.wo.weight"), self.wb("attn.wo.bias"), residual=x)
             h2, _, mu2, rs2 = ops.norm_fwd(x2, self.w("ffn_norm.weight"), self.wb("ffn_norm.bias"), kind=kind,
                                            eps=cfg.norm_eps)
@@ -506,6 +512,7 @@ class Block:
         st = ctx.layers[self.i]
         if len(st) == 1 and "x" in st:  # recompute the stash
             tmp = MBContext(ctx.mb, ctx.seed)
+            tmp.docs = ctx.docs
             self.forward(st["x"], B, S, tmp, recompute=False)
             ctx.layers[self.i] = tmp.layers[self.i]
         return ctx.layers[self.i]
@@ -562,10 +569,14 @@ class Block:
             dq, dk, dv = dqkv[:, : H * Dh], dqkv[:, H * Dh:(H + KV) * Dh], dqkv[:, (H + KV) * Dh:]
             # the QKV bias gradient is summed by the attention backward kernels themselves
             # (no second pass over dQKV), unless RoPE still has to rotate dQ/dK afterwards
-            fuse_qkv_bias = cfg.bias and cfg.pos != "rope" and _FUSE_QKV_BIAS
+            # (the document-masked kernels have no fused sums: the separate colsum job runs)
+            docs = ctx.docs
+            fuse_qkv_bias = cfg.bias and cfg.pos != "rope" and _FUSE_QKV_BIAS and docs is None
             ops.attn_bwd(q, k, v, o, do, st["lse"], dq, dk, dv, B, S, S, H, KV, Dh, cfg.causal,
                          p_drop=cfg.dropout, seed=_seed(sd, 1),
-                         dbias=self.g("attn.wqkv.bias") if fuse_qkv_bias else None)
+                         dbias=self.g("attn.wqkv.bias") if fuse_qkv_bias else None,
+                         doc_start=docs[0] if docs is not None else None,
+                         doc_end=docs[1] if docs is not None else None)
             if cfg.pos == "rope":
                 ops.rope_(dqkv, self.rope[0], self.rope[1], S, H, KV, Dh, inverse=True)
             h1 = st["h1"]
@@ -988,12 +999,24 @@ class NativeModel:
 
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor, ctx: MBContext, B: int, S: int, target: Optional[torch.Tensor] = None,
-                loss_scale: float = 1.0, keep_logits: bool = False):
+                loss_scale: float = 1.0, keep_logits: bool = False,
+                docs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
         """x: tokens [B,S] (stage 0) or hidden [B*S, D].  Last stage: returns the mean
         loss (f32 scalar tensor) and keeps dlogits for the backward (the fused CE writes
         the gradient over the logits; ``keep_logits`` saves a copy first, in
-        ``ctx.misc['logits_out']``, for callers that want the outputs too)."""
+        ``ctx.misc['logits_out']``, for callers that want the outputs too).
+
+        ``docs``: the (doc_start, doc_end) pair of ``ops.doc_bounds`` for this microbatch
+        (int32 [B*S] each): attention stays inside each packed document.  It is kept on
+        ``ctx`` for the backward and the recompute path.  Causal pre-norm decoders only;
+        positions are not reset per document."""
         cfg = self.cfg
+        if docs is not None:
+            if cfg.cross_attn or not cfg.causal:
+                raise ValueError("docs: the document mask needs a causal pre-norm decoder")
+            if len(docs) != 2:
+                raise ValueError("docs: expected the pair (doc_start, doc_end)")
+            ctx.docs = (docs[0], docs[1])
         if self.first:
             tokens = x.reshape(-1)
             h = ops.embed_fwd(tokens, self._emb_arena().w("tok_embeddings.weight"),

@@ -1,7 +1,7 @@
 """Adapter between :class:`~mipipe.models.native.NativeModel` and the pipeline runtime."""
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -25,7 +25,9 @@ class NativeStage(StageBase):
     """
 
     def __init__(self, model: NativeModel, mbs: int, seq_len: int, dp_group=None, embed_group=None,
-                 seed: int = 1234, graphs: bool = False):
+                 seed: int = 1234, graphs: bool = False, doc_mask_mbs: int = 0):
+        """``doc_mask_mbs``: > 0 turns the packed-document mask on for that many microbatches
+        per step (models/native.py, ``docs``); 0: plain causal attention."""
         self.model = model
         self.cfg: NativeConfig = model.cfg
         self.stage_index = model.stage_index
@@ -48,6 +50,15 @@ class NativeStage(StageBase):
         else:  # hidden states (the last stage's final-norm output with a distributed head)
             self.output_specs = [((T, D), model.arena.dtype)]
         self._ctx = {}
+        # packed-document bounds: persistent int32 (doc_start, doc_end) buffers per microbatch,
+        # allocated once.  ``set_docs`` refreshes them before a step; eager, graphed and
+        # tape-replayed forwards and backwards all read these same buffers, so a captured
+        # graph sees every step's boundaries.  They start as one document per row.
+        self._docs: List[Tuple[torch.Tensor, torch.Tensor]] = []
+        for _ in range(doc_mask_mbs):
+            ds = torch.zeros(T, dtype=torch.int32, device=model.device)
+            de = torch.full((T,), seq_len - 1, dtype=torch.int32, device=model.device)
+            self._docs.append((ds, de))
         # HIP graphs (parallel/graphs.py): step 1 runs eagerly (lazy kernel init), every
         # (op, microbatch) action is captured on its first later use and replayed after
         # (dropout stays graph-safe: kernels mix a device-side step counter into their
@@ -97,6 +108,17 @@ class NativeStage(StageBase):
     def _graphed(self) -> bool:
         return self.graphs is not None and self.step_id > 1
 
+    def set_docs(self, doc_start: torch.Tensor, doc_end: torch.Tensor) -> None:
+        """Copy the step's bounds ([m*mbs*S] int32, microbatch-major like the token batch)
+        into the per-microbatch buffers, on the current (compute) stream."""
+        T = self.mbs * self.S
+        for mb, (ds, de) in enumerate(self._docs):
+            ds.copy_(doc_start[mb * T:(mb + 1) * T], non_blocking=True)
+            de.copy_(doc_end[mb * T:(mb + 1) * T], non_blocking=True)
+
+    def _docs_of(self, mb: int):
+        return self._docs[mb] if self._docs else None
+
     @property
     def arena(self):
         return self.model.arena
@@ -119,7 +141,7 @@ class NativeStage(StageBase):
             ctx.misc["logits_dst"] = self._logits_dst(mb)
         x = args[0]
         out = self.model.forward(x, ctx, self.mbs, self.S, target=target if self.is_last else None,
-                                 loss_scale=loss_scale, keep_logits=want_logits)
+                                 loss_scale=loss_scale, keep_logits=want_logits, docs=self._docs_of(mb))
         self._ctx[mb] = ctx
         if self.is_last and not self.split_head:
             if target is None:
@@ -183,7 +205,7 @@ class NativeStage(StageBase):
             if want_logits:
                 ctx.misc["logits_dst"] = self._logits_dst(mb)
             out = self.model.forward(ins[0], ctx, self.mbs, self.S, target=ins[1] if last_loss else None,
-                                     loss_scale=loss_scale, keep_logits=want_logits)
+                                     loss_scale=loss_scale, keep_logits=want_logits, docs=self._docs_of(mb))
             self._gctx[mb] = ctx
             if want_logits:
                 # the logits copy is a graph output: persistent, refreshed by every replay

@@ -29,7 +29,14 @@ def _rope(x, S, theta):  # x [B, h, S, Dh], rotate-half
     return torch.cat([a * c - b * s, b * c + a * s], -1)
 
 
-def _attn(cfg, q, k, v, B, S, causal):
+def _doc_visible(docs, B, S, device):
+    """bool [B, 1, S, S]: key j visible to query i iff doc_start[i] <= j <= i."""
+    ds = docs[0].reshape(B, S).to(device).long()
+    i, j = torch.arange(S, device=device)[:, None], torch.arange(S, device=device)[None, :]
+    return ((j <= i)[None] & (j[None] >= ds[:, :, None]))[:, None]
+
+
+def _attn(cfg, q, k, v, B, S, causal, docs=None):
     H, KV, Dh = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
     q = q.reshape(B, S, H, Dh).transpose(1, 2)
     k = k.reshape(B, S, KV, Dh).transpose(1, 2)
@@ -38,13 +45,20 @@ def _attn(cfg, q, k, v, B, S, causal):
         q, k = _rope(q, S, cfg.rope_theta), _rope(k, S, cfg.rope_theta)
     rep = H // KV
     k, v = k.repeat_interleave(rep, 1), v.repeat_interleave(rep, 1)
-    o = F.scaled_dot_product_attention(q, k, v, is_causal=causal)
+    if docs is not None:
+        o = F.scaled_dot_product_attention(q, k, v, attn_mask=_doc_visible(docs, B, S, q.device))
+    else:
+        o = F.scaled_dot_product_attention(q, k, v, is_causal=causal)
     return o.transpose(1, 2).reshape(B * S, H * Dh)
 
 
 def forward_loss(cfg: NativeConfig, P: Dict[str, torch.Tensor], tokens: torch.Tensor, targets: torch.Tensor,
-                 layers=None) -> torch.Tensor:
+                 layers=None, docs=None) -> torch.Tensor:
+    """``docs``: the (doc_start, doc_end) pair of ``ops.doc_bounds`` (int32 [B*S]): attention
+    stays inside each packed document (causal pre-norm decoders)."""
     B, S = tokens.shape
+    if docs is not None and (cfg.cross_attn or not cfg.causal):
+        raise ValueError("docs: the document mask needs a causal pre-norm decoder")
     d = cfg.d_model
     x = P["tok_embeddings.weight"][tokens.reshape(-1)]
     if cfg.pos == "learned":
@@ -73,7 +87,7 @@ def forward_loss(cfg: NativeConfig, P: Dict[str, torch.Tensor], tokens: torch.Te
         if cfg.bias:
             qkv = qkv + p("attn.wqkv.bias")
         H, KV, Dh = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
-        o = _attn(cfg, qkv[:, :H * Dh], qkv[:, H * Dh:(H + KV) * Dh], qkv[:, (H + KV) * Dh:], B, S, cfg.causal)
+        o = _attn(cfg, qkv[:, :H * Dh], qkv[:, H * Dh:(H + KV) * Dh], qkv[:, (H + KV) * Dh:], B, S, cfg.causal, docs)
         o = o @ p("attn.wo.weight").t()
         if cfg.bias:
             o = o + p("attn.wo.bias")

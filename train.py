@@ -104,7 +104,14 @@ def main():
                               layer_ranges=[tuple(r) for r in p.layer_ranges] if p.layer_ranges else None,
                               split_head=p.split_head,
                               dtype=torch.bfloat16 if device.type == "cuda" else torch.float32,
-                              graphs=(device.type == "cuda") if t.graphs is None else bool(t.graphs))
+                              graphs=(device.type == "cuda") if t.graphs is None else bool(t.graphs),
+                              doc_mask=t.doc_eos is not None)
+    # packed documents (train.doc_eos): every rank builds the batch, so every rank derives
+    # the document bounds from it and nothing extra travels over p2p
+    from mipipe import ops
+
+    def docs_of(x):
+        return ops.doc_bounds(x, t.doc_eos) if t.doc_eos is not None else None
     start = 0
     if t.resume:
         man = trainer.load_checkpoint(t.resume)
@@ -116,7 +123,8 @@ def main():
         # HIP graphs: two setup passes on the first batch capture every per-microbatch
         # action (gradients discarded, weights untouched); later steps replay them, from
         # the native stage runner once one step has been recorded
-        trainer.capture_graphs(*data.batch(start))
+        x0, y0 = data.batch(start)
+        trainer.capture_graphs(x0, y0, docs=docs_of(x0))
     log = MetricsLogger(t.metrics_file, rank, device)
     wd = Watchdog(t.watchdog_s, describe=trainer.describe)
     tokens_per_step = p.dp * m * t.micro_batch * t.seq_len
@@ -125,7 +133,7 @@ def main():
         lr = lr_at(step, t)
         t0 = time.perf_counter()
         with wd.step():
-            loss = trainer.train_step(x, y, lr=lr)
+            loss = trainer.train_step(x, y, lr=lr, docs=docs_of(x))
             if device.type == "cuda":
                 torch.cuda.synchronize()
         dt = time.perf_counter() - t0
