@@ -94,6 +94,10 @@ int mp_gemm2_has_probe_engines();
 int mp_gemm_tt_grouped(int n, const void* const* A, const void* const* B, float* const* C, const int* M, const int* N,
                        const int* K, const int64_t* lda, const int64_t* ldb, const int64_t* ldc, float alpha,
                        hipStream_t st);
+int mp_gemm3_tt_grouped_plan(int n, const int* M, const int* N, int K, int force_split, int64_t* ws_floats);
+int mp_gemm3_tt_grouped(int n, const void* const* A, const void* const* B, float* const* C, const int* M, const int* N,
+                        int K, const int64_t* lda, const int64_t* ldb, const int64_t* ldc, float alpha, int S, float* ws,
+                        hipStream_t st);
 int mp_probe_spin(unsigned* flag, unsigned expect, int64_t timeout_us, unsigned* result, hipStream_t waiter);
 int mp_probe_set(unsigned* flag, unsigned value, hipStream_t setter);
 int mp_probe_clock_khz();
@@ -754,6 +758,56 @@ void gemm_tt_grouped(std::vector<torch::Tensor> dy, std::vector<torch::Tensor> x
   check(mp_gemm_tt_grouped(n, A, B, Cp, M, N, K, lda, ldb, ldc, (float)alpha, cur_stream()), "gemm_tt_grouped");
 }
 
+// grouped long-token weight-gradient GEMMs: C[i] (f32 [N_i, K_i]) += alpha * dy[i]^T x[i]
+// (dy [T, N_i], x [T, K_i] bf16, unit inner stride, ONE token count T for the group) in one
+// launch of 256x256 tiles at a common split-K factor (split = 0: the planner's; > 0: forced,
+// clamped to T / 64) plus one reduce launch when that factor is > 1.  Returns the factor used.
+int64_t gemm_dw_grouped(std::vector<torch::Tensor> dy, std::vector<torch::Tensor> x, std::vector<torch::Tensor> C,
+                        double alpha, int64_t split) {
+  const char* fn = "gemm_dw_grouped";
+  const int n = (int)dy.size();
+  TORCH_CHECK(n == (int)x.size() && n == (int)C.size() && n >= 1 && n <= 8, fn, ": 1..8 problems");
+  TORCH_CHECK(split >= 0 && split <= INT_MAX, fn, ": split ", split, " must be >= 0");
+  const void* A[8];
+  const void* B[8];
+  float* Cp[8];
+  int M[8], N[8];
+  int64_t lda[8], ldb[8], ldc[8];
+  TORCH_CHECK(dy[0].is_cuda(), fn, ": dy must be on the GPU");
+  const int64_t T = dy[0].dim() == 2 ? dy[0].size(0) : 0;
+  for (int i = 0; i < n; ++i) {
+    gemm_operand(fn, "dy", dy[i], torch::kBFloat16, dy[0]);
+    gemm_operand(fn, "x", x[i], torch::kBFloat16, dy[0]);
+    gemm_operand(fn, "C", C[i], torch::kFloat32, dy[0]);
+    TORCH_CHECK(dy[i].size(0) == T && x[i].size(0) == T, fn, ": every dy and x needs the same token count T = ", T,
+                ", problem ", i, " has ", dy[i].size(0), " and ", x[i].size(0));
+    TORCH_CHECK(C[i].size(0) == dy[i].size(1) && C[i].size(1) == x[i].size(1), fn, ": C[", i, "] must be [",
+                dy[i].size(1), ", ", x[i].size(1), "]");
+    TORCH_CHECK(dy[i].size(1) % 8 == 0 && x[i].size(1) % 8 == 0, fn, ": problem ", i, ": M = ", dy[i].size(1),
+                " and N = ", x[i].size(1), " must be multiples of 8");
+    TORCH_CHECK(dy[i].size(1) <= INT_MAX && x[i].size(1) <= INT_MAX, fn, ": M, N must fit 32 bits");
+    A[i] = dy[i].data_ptr();
+    B[i] = x[i].data_ptr();
+    Cp[i] = C[i].data_ptr<float>();
+    M[i] = (int)dy[i].size(1);
+    N[i] = (int)x[i].size(1);
+    lda[i] = dy[i].stride(0);
+    ldb[i] = x[i].stride(0);
+    ldc[i] = C[i].stride(0);
+  }
+  TORCH_CHECK(T % 64 == 0 && T <= INT_MAX, fn, ": T = ", T, " must be a multiple of 64");
+  // split-K slabs from the caching allocator on the current stream (graph captures take
+  // them from their private pool), as gemm2() does
+  int64_t ws_n = 0;
+  const int S = mp_gemm3_tt_grouped_plan(n, M, N, (int)T, (int)split, &ws_n);
+  torch::Tensor ws;
+  if (ws_n > 0) ws = torch::empty({ws_n}, C[0].options().dtype(torch::kFloat32));
+  check(mp_gemm3_tt_grouped(n, A, B, Cp, M, N, (int)T, lda, ldb, ldc, (float)alpha, S,
+                            ws.defined() ? ws.data_ptr<float>() : nullptr, cur_stream()),
+        fn);
+  return S;
+}
+
 void transpose(torch::Tensor in, torch::Tensor out) {
   TORCH_CHECK(in.is_cuda() && out.is_cuda() && in.get_device() == out.get_device(), "transpose: in and out must be on one GPU");
   TORCH_CHECK(in.scalar_type() == torch::kBFloat16 && out.scalar_type() == torch::kBFloat16, "transpose: in and out must be bf16");
@@ -969,6 +1023,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lane_merge", &lane_merge, pybind11::arg("g0"), pybind11::arg("lanes"), pybind11::arg("sumsq") = pybind11::none());
   m.def("gemm_tt_grouped", &gemm_tt_grouped, pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("C"),
         pybind11::arg("alpha") = 1.0);
+  m.def("gemm_dw_grouped", &gemm_dw_grouped, pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("C"),
+        pybind11::arg("alpha") = 1.0, pybind11::arg("split") = 0);
   m.def("gemm2", &gemm2, pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("C"), pybind11::arg("bias"),
         pybind11::arg("residual"), pybind11::arg("aux"), pybind11::arg("transA"), pybind11::arg("transB"),
         pybind11::arg("epilogue"), pybind11::arg("accum"), pybind11::arg("alpha"), pybind11::arg("force_cfg"),

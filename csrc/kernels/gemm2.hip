@@ -17,6 +17,8 @@
 //   images) or two ds_read_b64_tr_b16 (outer-contiguous images).
 // * Epilogue staged through LDS one wave-row group at a time -> coalesced 16-byte bias /
 //   residual / activation / store, or lane-consecutive f32 atomics for split-K.
+#include <climits>
+
 #include "mp_common.h"
 
 using namespace mp;
@@ -712,34 +714,21 @@ __global__ void __launch_bounds__(NT, 2) __attribute__((amdgpu_waves_per_eu(2, 2
 // every SIMD one wave issues MFMAs while its partner issues ds_reads / DMA: the
 // cdna guide's 8-phase template (§5 "256^2 8-phase template"), with 32x32x16 MFMAs.
 // ---------------------------------------------------------------------------------------
-template <int EPI, bool ACC, bool M16, bool TT = false>
-__global__ void __launch_bounds__(NT, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
-gemm3_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, void* __restrict__ Cv,
-             const bf16_t* __restrict__ bias, const bf16_t* __restrict__ R, bf16_t* __restrict__ AUX,
-             float* __restrict__ WS, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr,
-             int64_t ldx, float alpha, float p_drop, uint64_t seed, int tile_lim) {
-  if (p_drop > 0.f) seed = step_seed(seed);
+// One 256x256 tile of gemm3: tile `wg` (raster order below) of K-slice `split` of `nsplit`.
+// gemm3_kernel and the grouped dW kernel (gemm3_tt_grouped_kernel) differ only in how a
+// workgroup finds (problem, wg, split).
+template <int EPI, bool ACC, bool M16, bool TT>
+__device__ __forceinline__ void gemm3_tile(char* smem, const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
+                                           void* __restrict__ Cv, const bf16_t* __restrict__ bias,
+                                           const bf16_t* __restrict__ R, bf16_t* __restrict__ AUX,
+                                           float* __restrict__ WS, int M, int N, int K, int64_t lda, int64_t ldb,
+                                           int64_t ldc, int64_t ldr, int64_t ldx, float alpha, float p_drop,
+                                           uint64_t seed, int tile_lim, int wg, int split, int nsplit) {
   constexpr int BM = 256, BN = 256, WM = 2, WN = 4;
   constexpr int HALF = 128 * 128;          // one half-tile image: 128 rows x 128 B
   constexpr int BUF = 4 * HALF;            // A0 A1 B0 B1
-  extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int gm = (M + BM - 1) / BM, gn = (N + BN - 1) / BN;
-  const int nwg = tile_lim > 0 ? tile_lim : gm * gn;
-  // split-K grids: workgroups are dealt to the 8 XCDs round-robin in LINEAR id order
-  // (x + gridDim.x * y), so remap that id, then cut it into (split, tile): an XCD's L2 holds
-  // the panels of ONE split's neighbouring tiles.  Remapping blockIdx.x alone assumed XCD =
-  // x % 8, which is wrong for y > 0 whenever gridDim.x % 8 != 0 and scattered the tiles that
-  // share a panel over all XCDs (the dW GEMMs read ~4x their unique bytes from HBM)
-  int wg, split;
-  if (gridDim.y > 1 && tile_lim == 0) {   // (tile_lim = -1: the x-only remap, the default)
-    const int v = xcd_remap((int)blockIdx.x + (int)gridDim.x * (int)blockIdx.y, nwg * (int)gridDim.y);
-    split = v / nwg;
-    wg = v % nwg;
-  } else {
-    wg = xcd_remap((int)blockIdx.x, nwg);
-    split = (int)blockIdx.y;
-  }
   constexpr int GROUP = MP_G3_GROUP;   // tile rows per raster group (L2 reuse of the A panels)
   const int group = wg / (GROUP * gn);
   const int first_m = group * GROUP;
@@ -754,7 +743,6 @@ gemm3_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, void* _
   const int wr = wave / WN, wc = wave % WN;
   const int wm = wr * (BM / WM), wn = wc * (BN / WN);
 
-  const int nsplit = gridDim.y;
   const int ktiles = K / BK;
   const int kt0 = split * ktiles / nsplit;
   const int nk = (split + 1) * ktiles / nsplit - kt0;
@@ -1039,6 +1027,102 @@ gemm3_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, void* _
   __syncthreads();
   epilogue<BM, BN, WM, WN, EPI, ACC>(Stage16<8, 4>{acc, wn, lane}, smem, m0, n0, wr, Cv, bias, R, AUX, WS, M, N, ldc,
                                      ldr, ldx, alpha, nsplit, p_drop, seed, nullptr, 0, 0, split);
+  }
+}
+
+template <int EPI, bool ACC, bool M16, bool TT = false>
+__global__ void __launch_bounds__(NT, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
+gemm3_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, void* __restrict__ Cv,
+             const bf16_t* __restrict__ bias, const bf16_t* __restrict__ R, bf16_t* __restrict__ AUX,
+             float* __restrict__ WS, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr,
+             int64_t ldx, float alpha, float p_drop, uint64_t seed, int tile_lim) {
+  if (p_drop > 0.f) seed = step_seed(seed);
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nwg = tile_lim > 0 ? tile_lim : ((M + 255) / 256) * ((N + 255) / 256);
+  // split-K grids: workgroups are dealt to the 8 XCDs round-robin in LINEAR id order
+  // (x + gridDim.x * y), so remap that id, then cut it into (split, tile): an XCD's L2 holds
+  // the panels of ONE split's neighbouring tiles.  Remapping blockIdx.x alone assumed XCD =
+  // x % 8, which is wrong for y > 0 whenever gridDim.x % 8 != 0 and scattered the tiles that
+  // share a panel over all XCDs (the dW GEMMs read ~4x their unique bytes from HBM)
+  int wg, split;
+  if (gridDim.y > 1 && tile_lim == 0) {   // (tile_lim = -1: the x-only remap, the default)
+    const int v = xcd_remap((int)blockIdx.x + (int)gridDim.x * (int)blockIdx.y, nwg * (int)gridDim.y);
+    split = v / nwg;
+    wg = v % nwg;
+  } else {
+    wg = xcd_remap((int)blockIdx.x, nwg);
+    split = (int)blockIdx.y;
+  }
+  gemm3_tile<EPI, ACC, M16, TT>(smem, A, B, Cv, bias, R, AUX, WS, M, N, K, lda, ldb, ldc, ldr, ldx, alpha, p_drop, seed,
+                                tile_lim, wg, split, (int)gridDim.y);
+}
+
+// ---------------------------------------------------------------------------------------
+// Grouped long-token weight-gradient GEMMs: up to MP_GROUP_MAX TT problems
+// C_g[M_g, N_g] (f32) += alpha * A_g^T B_g over ONE common K (a microbatch's tokens), 256x256
+// tiles of gemm3's TT build, one split factor S for the group: grid = S * (sum of tiles).
+// One at a time, a layer's four dW GEMMs are 9-36 tiles each and need split 7-28 to cover
+// 256 CUs (choose()): ~1000 f32 partial tiles per layer through HBM and back plus four reduce
+// launches.  Together their 108 tiles fill the chip at S = 2.
+//
+// Mapping: the XCD-remapped id v walks problem -> split -> tile (gemm3's raster), so the
+// workgroups that run together on an XCD (consecutive v) are neighbouring tiles of one
+// problem and one split and share its A / B panels in that XCD's L2.
+// S > 1: partial tiles go to slabs ws[elem_start[g] * S + s * M_g * N_g] (row stride N_g) and
+// splitk_reduce_grouped_kernel adds them into C_g in split order; S = 1: read-modify-write of
+// C_g in the epilogue, no workspace.
+// ---------------------------------------------------------------------------------------
+struct GroupTT3 {
+  const bf16_t* A[MP_GROUP_MAX];
+  const bf16_t* B[MP_GROUP_MAX];
+  float* C[MP_GROUP_MAX];
+  int64_t lda[MP_GROUP_MAX], ldb[MP_GROUP_MAX], ldc[MP_GROUP_MAX];
+  int64_t elem_start[MP_GROUP_MAX + 1];   // prefix sums of M_g * N_g
+  int M[MP_GROUP_MAX], N[MP_GROUP_MAX];
+  int tile_start[MP_GROUP_MAX + 1];       // prefix sums of the 256x256 tile counts
+  int n, K, S;
+  float alpha;
+  float* ws;
+};
+
+__global__ void __launch_bounds__(NT, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
+gemm3_tt_grouped_kernel(const GroupTT3 g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int total = g.tile_start[g.n];
+  const int v = xcd_remap((int)blockIdx.x, total * g.S);
+  int p = 0;
+#pragma unroll
+  for (int i = 1; i < MP_GROUP_MAX; ++i)
+    if (i < g.n && v >= g.tile_start[i] * g.S) p = i;
+  const int tiles = g.tile_start[p + 1] - g.tile_start[p];
+  const int local = v - g.tile_start[p] * g.S;
+  const int split = local / tiles, wg = local % tiles;
+  float* ws = g.S > 1 ? g.ws + g.elem_start[p] * g.S : nullptr;
+  gemm3_tile<EPI_NONE, true, true, true>(smem, g.A[p], g.B[p], g.C[p], nullptr, nullptr, nullptr, ws, g.M[p], g.N[p],
+                                         g.K, g.lda[p], g.ldb[p], g.ldc[p], 0, 0, g.alpha, 0.f, 0, 0, wg, split, g.S);
+}
+
+// C_g[M_g, N_g] (row stride ldc_g) += the group's split-K slabs, summed in split order
+__global__ void __launch_bounds__(256) splitk_reduce_grouped_kernel(const GroupTT3 g) {
+  const int64_t n4 = g.elem_start[g.n] / 4;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const int64_t e = i * 4;
+    int p = 0;
+#pragma unroll
+    for (int j = 1; j < MP_GROUP_MAX; ++j)
+      if (j < g.n && e >= g.elem_start[j]) p = j;
+    const int64_t le = e - g.elem_start[p], slab = (int64_t)g.M[p] * g.N[p];
+    const float* w = g.ws + g.elem_start[p] * g.S + le;
+    const int m = (int)(le / g.N[p]), n = (int)(le % g.N[p]);
+    float4 acc = *reinterpret_cast<const float4*>(w);
+    for (int s = 1; s < g.S; ++s) {
+      const float4 t = *reinterpret_cast<const float4*>(w + s * slab);
+      acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w;
+    }
+    float4* cp = reinterpret_cast<float4*>(g.C[p] + (int64_t)m * g.ldc[p] + n);
+    float4 c = *cp;
+    c.x += acc.x; c.y += acc.y; c.z += acc.z; c.w += acc.w;
+    *cp = c;
   }
 }
 
@@ -2583,6 +2667,41 @@ static int choose(int M, int N, int K, bool acc, bool outer, int* split_out) {
   return best;
 }
 
+// The common split-K factor of a grouped dW launch (gemm3_tt_grouped_kernel) of `tiles`
+// 256x256 tiles over kt K-tiles.  The K-loop work does not depend on S; the slab traffic
+// (2 x S x 256 KiB per tile) and the reduce pass grow with it.  So: the SMALLEST S whose
+// tiles * S workgroups fill their ceil(tiles * S / 256) rounds of CUs to >= 80 % (S = 1, no
+// slabs at all, where the tiles alone do), at >= 4 K-tiles per workgroup and within
+// MIPIPE_DW_MAXSPLIT; where no S gets there, the best-filling one.  GPT-2 small's layer
+// (108 tiles): S = 2, 216 workgroups.  force > 0 (or MIPIPE_DW_GROUP_SPLIT) sets S, clamped
+// to the K-tiles.
+static int choose_group_split(int tiles, int kt, int force) {
+  static const int env_force = [] {
+    const char* e = getenv("MIPIPE_DW_GROUP_SPLIT");
+    return e ? atoi(e) : 0;
+  }();
+  static const int cap = [] {
+    const char* e = getenv("MIPIPE_DW_MAXSPLIT");
+    const int v = e ? atoi(e) : 32;
+    return v > 0 ? v : 32;
+  }();
+  if (force <= 0) force = env_force;
+  if (force > 0) return force < kt ? force : (kt > 0 ? kt : 1);
+  const int smax = kt / 4 < cap ? kt / 4 : cap;
+  int best = 1;
+  float best_fill = 0.f;
+  for (int s = 1; s <= (smax > 1 ? smax : 1); ++s) {
+    const int work = tiles * s, rounds = (work + 255) / 256;
+    const float fill = (float)work / (float)(rounds * 256);
+    if (fill >= 0.8f) return s;
+    if (fill > best_fill) {
+      best_fill = fill;
+      best = s;
+    }
+  }
+  return best;
+}
+
 }  // namespace g2
 
 using namespace g2;
@@ -2984,4 +3103,74 @@ extern "C" int mp_gemm_tt_grouped(int n, const void* const* A, const void* const
   }
   gemms_tt_grouped_kernel<<<t, 256, LDS, st>>>(g);
   return (int)hipGetLastError();
+}
+
+// split-K factor a grouped long-token dW launch will use (force_split > 0 or
+// MIPIPE_DW_GROUP_SPLIT set it) and the f32 workspace it needs: S * sum(M_g * N_g) for S > 1
+extern "C" int mp_gemm3_tt_grouped_plan(int n, const int* M, const int* N, int K, int force_split,
+                                        int64_t* ws_floats) {
+  int tiles = 0;
+  int64_t elems = 0;
+  for (int i = 0; i < n; ++i) {
+    tiles += ((M[i] + 255) / 256) * ((N[i] + 255) / 256);
+    elems += (int64_t)M[i] * N[i];
+  }
+  const int S = choose_group_split(tiles, K / BK, force_split);
+  *ws_floats = S > 1 ? (int64_t)S * elems : 0;
+  return S;
+}
+
+// C_g += alpha * A_g^T B_g for n <= MP_GROUP_MAX problems over one common K (A_g [K][M_g],
+// B_g [K][N_g] bf16 k-major, C_g f32 [M_g][N_g] row stride ldc_g): one launch of 256x256
+// tiles at split S (from mp_gemm3_tt_grouped_plan; ws holds its workspace) plus, for S > 1,
+// one reduce launch.  -1 if a shape does not fit (M, N multiples of 8, K of 64, 1 <= S <= K / 64)
+extern "C" int mp_gemm3_tt_grouped(int n, const void* const* A, const void* const* B, float* const* C, const int* M,
+                                   const int* N, int K, const int64_t* lda, const int64_t* ldb, const int64_t* ldc,
+                                   float alpha, int S, float* ws, hipStream_t st) {
+  if (n <= 0) return 0;
+  if (n > MP_GROUP_MAX || K <= 0 || K % BK || S < 1 || S > K / BK || (S > 1 && ws == nullptr)) return -1;
+  GroupTT3 g{};
+  g.n = n;
+  g.K = K;
+  g.S = S;
+  g.alpha = alpha;
+  g.ws = ws;
+  int t = 0;
+  int64_t e = 0;
+  for (int i = 0; i < n; ++i) {
+    if (M[i] % 8 || N[i] % 8 || M[i] <= 0 || N[i] <= 0) return -1;
+    g.A[i] = (const bf16_t*)A[i];
+    g.B[i] = (const bf16_t*)B[i];
+    g.C[i] = C[i];
+    g.M[i] = M[i];
+    g.N[i] = N[i];
+    g.lda[i] = lda[i];
+    g.ldb[i] = ldb[i];
+    g.ldc[i] = ldc[i];
+    g.tile_start[i] = t;
+    g.elem_start[i] = e;
+    t += ((M[i] + 255) / 256) * ((N[i] + 255) / 256);
+    e += (int64_t)M[i] * N[i];
+  }
+  for (int i = n; i <= MP_GROUP_MAX; ++i) {
+    g.tile_start[i] = t;
+    g.elem_start[i] = e;
+  }
+  if ((int64_t)t * S > INT_MAX) return -1;
+  constexpr int LDS_MAIN = 2 * 4 * 128 * 128;
+  constexpr int EPI_BYTES = 128 * (256 + 4) * 4;
+  constexpr int LDS = LDS_MAIN > EPI_BYTES ? LDS_MAIN : EPI_BYTES;
+  static bool attr = false;
+  if (!attr) {
+    hipFuncSetAttribute((const void*)gemm3_tt_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    attr = true;
+  }
+  gemm3_tt_grouped_kernel<<<t * S, NT, LDS, st>>>(g);
+  int rc = (int)hipGetLastError();
+  if (rc == 0 && S > 1) {
+    const int blocks = (int)std::min<int64_t>((e / 4 + 255) / 256, 4096);
+    splitk_reduce_grouped_kernel<<<blocks, 256, 0, st>>>(g);
+    rc = (int)hipGetLastError();
+  }
+  return rc;
 }

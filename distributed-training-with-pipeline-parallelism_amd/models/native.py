@@ -582,7 +582,7 @@ class Block:
             h1 = st["h1"]
             wjobs.append(ops.DW(dqkv, h1, self.g("attn.wqkv.weight")))
             if cfg.bias and not fuse_qkv_bias:
-                wjobs.append(lambda dqkv=dqkv: ops.colsum(dqkv, self.g("attn.wqkv.bias")))
+                wjobs.append(ops.ColSum(dqkv, self.g("attn.wqkv.bias")))
             dh1 = ops.linear_dx(dqkv, self.w("attn.wqkv.weight"), wt=self.wt("attn.wqkv.weight"))
             dx, _ = ops.norm_bwd(dh1, st["x"], self.w("attn_norm.weight"), st["mu1"], st["rs1"], kind=kind,
                                  dres=dx2, dw=self.g("attn_norm.weight"), dbias=self.gb("attn_norm.bias"))
