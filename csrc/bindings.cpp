@@ -46,6 +46,13 @@ int mp_swiglu_fwd(const void* gu, void* y, int T, int F, hipStream_t st);
 int mp_swiglu_bwd(const void* gu, const void* dy, void* dgu, int T, int F, hipStream_t st);
 int mp_rope(void* qkv, const float* cs, const float* sn, int T, int S, int H, int Hkv, int Dh, int pos_offset,
             int inverse, hipStream_t st);
+int mp_embed_pos(const int64_t* idx, const int* pos, const void* wte, const void* wpe, void* out, int B, int D,
+                 int n_tok, int n_pos, int f32, hipStream_t st);
+int mp_rope_kv_append(void* qkv, const float* cs, const float* sn, void* kc, void* vc, const int* pos,
+                      const uint8_t* active, int B, int H, int Hkv, int Dh, int Smax, int64_t qkv_ld, int64_t k_bs,
+                      int64_t k_ts, int64_t v_bs, int64_t v_ts, int rope, hipStream_t st);
+int mp_sample(const void* logits, int64_t ld, const float* u, uint8_t* done, int64_t* out, int B, int V, int Vp,
+              float temperature, int top_k, float top_p, int stop_token, int pad_token, int f32, hipStream_t st);
 int mp_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int Sq, int Sk, int H,
                 int Hkv, int D, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, int causal,
                 float scale, float p_drop, uint64_t seed, hipStream_t st);
@@ -609,6 +616,125 @@ int64_t attn_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cach
   return ns;
 }
 
+// ---- the ragged decode step (generate.hip): every position is read from device memory
+// a contiguous [B] vector of dtype dt on `ref`'s GPU (pos, active, u, done, out)
+void gen_vec(const char* fn, const char* name, const torch::Tensor& t, torch::ScalarType dt, int64_t B,
+             const torch::Tensor& ref) {
+  TORCH_CHECK(t.is_cuda() && t.get_device() == ref.get_device(), fn, ": ", name, " must be on the GPU of ",
+              "the other arguments");
+  TORCH_CHECK(t.scalar_type() == dt, fn, ": ", name, " must be ", dt, ", got ", t.scalar_type());
+  TORCH_CHECK(t.is_contiguous() && t.numel() == B, fn, ": ", name, " must be contiguous with one element per ",
+              "sequence (", B, "), got ", t.numel());
+}
+
+bool gen_aligned(const torch::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
+
+// out[b, :] = wte[idx[b], :] (+ wpe[pos[b], :]); pos: int32 [B] on the device
+void embed_pos(torch::Tensor idx, torch::Tensor pos, torch::Tensor wte, c10::optional<torch::Tensor> wpe,
+               torch::Tensor out) {
+  const int f32 = storage(out, "out");
+  const auto dt = out.scalar_type();
+  req(out, dt, "out");
+  req(wte, dt, "wte");
+  TORCH_CHECK(wte.dim() == 2 && wte.size(0) >= 1 && wte.size(0) <= INT_MAX && wte.size(1) % 8 == 0,
+              "embed_pos: wte must be [vocab, D] with D a multiple of 8");
+  const int64_t D = wte.size(1), B = idx.numel();
+  TORCH_CHECK(B >= 1 && B <= INT_MAX && out.numel() == B * D, "embed_pos: out must be [B, D]");
+  TORCH_CHECK(wte.get_device() == out.get_device(), "embed_pos: wte is on another device than out");
+  gen_vec("embed_pos", "idx", idx, torch::kInt64, B, out);
+  gen_vec("embed_pos", "positions", pos, torch::kInt32, B, out);
+  int64_t n_pos = 0;
+  if (wpe.has_value()) {
+    req(*wpe, dt, "wpe");
+    TORCH_CHECK(wpe->dim() == 2 && wpe->size(1) == D && wpe->size(0) >= 1 && wpe->size(0) <= INT_MAX &&
+                    wpe->get_device() == out.get_device(), "embed_pos: wpe must be [positions, D] on out's device");
+    n_pos = wpe->size(0);
+  }
+  check(mp_embed_pos(idx.data_ptr<int64_t>(), pos.data_ptr<int>(), wte.data_ptr(), ptr_or_null(wpe), out.data_ptr(),
+                     (int)B, (int)D, (int)wte.size(0), (int)n_pos, f32, cur_stream()),
+        "embed_pos");
+}
+
+// qkv: [B, (H + 2 Hkv) Dh] rows (one token per sequence); caches: [B, Smax, Hkv * Dh] views;
+// pos: int32 [B]; active: uint8 [B] (optional).  The RoPE tables must cover every position
+// the clamp can produce: Smax rows.
+void rope_kv_append(torch::Tensor qkv, c10::optional<torch::Tensor> cs, c10::optional<torch::Tensor> sn,
+                    torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor pos,
+                    c10::optional<torch::Tensor> active, int64_t H, int64_t Hkv, int64_t Dh, bool rope) {
+  const char* fn = "rope_kv_append";
+  TORCH_CHECK(Dh == 64 || Dh == 128, fn, ": head_dim ", Dh, " is not supported (64 or 128)");
+  TORCH_CHECK(H >= 1 && Hkv >= 1 && H <= 65535 && Hkv <= 65535, fn, ": bad head counts");
+  for (const torch::Tensor* t : {&qkv, &k_cache, &v_cache}) {
+    TORCH_CHECK(t->is_cuda() && t->get_device() == qkv.get_device(), fn, ": qkv / k_cache / v_cache must be on one GPU");
+    TORCH_CHECK(t->scalar_type() == torch::kBFloat16, fn, ": qkv / k_cache / v_cache must be bf16, got ",
+                t->scalar_type());
+  }
+  const int64_t width = (H + 2 * Hkv) * Dh;
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(1) == width && qkv.stride(1) == 1, fn, ": qkv must be [B, (H + 2 Hkv) Dh] rows");
+  const int64_t B = qkv.size(0);
+  TORCH_CHECK(B >= 1 && B <= 65535, fn, ": batch outside [1, 65535]");
+  TORCH_CHECK(k_cache.dim() == 3 && v_cache.dim() == 3 && k_cache.stride(2) == 1 && v_cache.stride(2) == 1,
+              fn, ": caches are [B, Smax, Hkv*Dh] with a unit inner stride");
+  const int64_t Smax = k_cache.size(1);
+  TORCH_CHECK(k_cache.size(0) == B && v_cache.size(0) == B && v_cache.size(1) == Smax && Smax >= 1 &&
+                  Smax <= INT_MAX && k_cache.size(2) == Hkv * Dh && v_cache.size(2) == Hkv * Dh, fn, ": cache shape");
+  TORCH_CHECK(gen_aligned(qkv) && gen_aligned(k_cache) && gen_aligned(v_cache) && (B == 1 || qkv.stride(0) % 8 == 0) &&
+                  k_cache.stride(0) % 8 == 0 && k_cache.stride(1) % 8 == 0 && v_cache.stride(0) % 8 == 0 &&
+                  v_cache.stride(1) % 8 == 0, fn, ": qkv / cache rows must be 16-byte aligned");
+  TORCH_CHECK(B == 1 || qkv.stride(0) >= width, fn, ": qkv rows overlap");
+  TORCH_CHECK(k_cache.stride(1) >= Hkv * Dh && v_cache.stride(1) >= Hkv * Dh &&
+                  (B == 1 || (k_cache.stride(0) >= Smax * k_cache.stride(1) && v_cache.stride(0) >= Smax * v_cache.stride(1))),
+              fn, ": cache rows overlap");
+  gen_vec(fn, "pos", pos, torch::kInt32, B, qkv);
+  if (active.has_value()) gen_vec(fn, "active", *active, torch::kUInt8, B, qkv);
+  const float* cp = nullptr;
+  const float* sp = nullptr;
+  if (rope) {
+    TORCH_CHECK(cs.has_value() && sn.has_value(), fn, ": rope needs the cos / sin tables");
+    for (const torch::Tensor* t : {&*cs, &*sn}) {
+      req(*t, torch::kFloat32, "cos / sin");
+      TORCH_CHECK(t->get_device() == qkv.get_device(), fn, ": cos / sin are on another device than qkv");
+      TORCH_CHECK(t->dim() == 2 && t->size(1) == Dh / 2 && t->size(0) >= Smax, fn, ": cos / sin must be [>= Smax = ",
+                  Smax, ", ", Dh / 2, "], got ", t->sizes());
+    }
+    cp = cs->data_ptr<float>();
+    sp = sn->data_ptr<float>();
+  }
+  check(mp_rope_kv_append(qkv.data_ptr(), cp, sp, k_cache.data_ptr(), v_cache.data_ptr(), pos.data_ptr<int>(),
+                          active.has_value() ? active->data_ptr<uint8_t>() : nullptr, (int)B, (int)H, (int)Hkv,
+                          (int)Dh, (int)Smax, qkv.stride(0), k_cache.stride(0), k_cache.stride(1), v_cache.stride(0),
+                          v_cache.stride(1), rope ? 1 : 0, cur_stream()),
+        fn);
+}
+
+// logits: [B, Vp] rows (bf16 or f32, any 16-byte aligned row stride >= Vp); u: f32 [B];
+// done: uint8 [B] (optional, read and written); out: int64 [B]
+void sample(torch::Tensor logits, int64_t V, torch::Tensor u, double temperature, int64_t top_k, double top_p,
+            c10::optional<torch::Tensor> done, int64_t stop_token, int64_t pad_token, torch::Tensor out) {
+  const char* fn = "sample";
+  TORCH_CHECK(logits.is_cuda(), fn, ": logits must be on the GPU");
+  const int f32 = storage(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.size(0) >= 1 && logits.size(1) >= 1,
+              fn, ": logits must be [B, Vp] rows with a unit inner stride");
+  const int64_t B = logits.size(0), Vp = logits.size(1), per = f32 ? 4 : 8;
+  TORCH_CHECK(B <= INT_MAX && Vp <= INT_MAX && Vp % 8 == 0, fn, ": Vp = ", Vp, " must be a multiple of 8");
+  TORCH_CHECK(V >= 1 && V <= Vp, fn, ": vocab ", V, " outside [1, Vp = ", Vp, "]");
+  const int64_t ld = B == 1 ? std::max<int64_t>(Vp, logits.stride(0) - logits.stride(0) % per) : logits.stride(0);
+  TORCH_CHECK(gen_aligned(logits) && ld % per == 0 && ld >= Vp, fn, ": logits rows must be 16-byte aligned and disjoint");
+  TORCH_CHECK(temperature >= 0.0, fn, ": temperature ", temperature, " must be >= 0");
+  TORCH_CHECK(top_k >= 0 && top_k <= INT_MAX, fn, ": top_k ", top_k, " must be >= 0");
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, fn, ": top_p ", top_p, " outside (0, 1]");
+  TORCH_CHECK(stop_token >= -1 && stop_token <= INT_MAX && pad_token >= 0 && pad_token <= INT_MAX,
+              fn, ": stop_token / pad_token out of range");
+  gen_vec(fn, "u", u, torch::kFloat32, B, logits);
+  gen_vec(fn, "out", out, torch::kInt64, B, logits);
+  if (done.has_value()) gen_vec(fn, "done", *done, torch::kUInt8, B, logits);
+  check(mp_sample(logits.data_ptr(), ld, u.data_ptr<float>(), done.has_value() ? done->data_ptr<uint8_t>() : nullptr,
+                  out.data_ptr<int64_t>(), (int)B, (int)V, (int)Vp, (float)temperature, (int)top_k, (float)top_p,
+                  (int)stop_token, (int)pad_token, f32, cur_stream()),
+        fn);
+}
+
 // ---- host-side argument checks of the GEMM bindings: every tensor a kernel will touch is
 // looked at before any launch, and the message names the argument
 bool aligned16(const torch::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
@@ -1019,6 +1145,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_plan", [](int64_t B, int64_t Hkv, int64_t max_len) {
     return mp_attn_decode_plan((int)B, (int)Hkv, (int)max_len);
   }, "key splits the decode attention picks for B sequences x Hkv KV heads over max_len keys");
+  m.def("embed_pos", &embed_pos);
+  m.def("rope_kv_append", &rope_kv_append);
+  m.def("sample", &sample);
   m.def("gemm", &gemm);
   m.def("lane_merge", &lane_merge, pybind11::arg("g0"), pybind11::arg("lanes"), pybind11::arg("sumsq") = pybind11::none());
   m.def("gemm_tt_grouped", &gemm_tt_grouped, pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("C"),

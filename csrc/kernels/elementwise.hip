@@ -9,6 +9,7 @@
 //   rope            rotate-half RoPE on the q/k heads of the packed qkv buffer, in place
 //                   (forward: +theta, backward: -theta), f32 cos/sin table from the host
 #include "mp_common.h"
+#include "mp_rope.h"
 
 #include <stdlib.h>
 
@@ -184,14 +185,7 @@ __global__ void __launch_bounds__(256) rope_kernel(bf16_t* __restrict__ qkv, con
     u16x4 x1 = *reinterpret_cast<u16x4*>(base + q4 * 4);
     u16x4 x2 = *reinterpret_cast<u16x4*>(base + half + q4 * 4);
     u16x4 o1, o2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int j = q4 * 4 + e;
-      const float c = cs[(int64_t)pos * half + j], s = sign * sn[(int64_t)pos * half + j];
-      const float a = bf2f(x1[e]), b = bf2f(x2[e]);
-      o1[e] = f2bf(a * c - b * s);
-      o2[e] = f2bf(b * c + a * s);
-    }
+    rope_rot4(x1, x2, cs + (int64_t)pos * half, sn + (int64_t)pos * half, q4 * 4, sign, o1, o2);
     *reinterpret_cast<u16x4*>(base + q4 * 4) = o1;
     *reinterpret_cast<u16x4*>(base + half + q4 * 4) = o2;
   }

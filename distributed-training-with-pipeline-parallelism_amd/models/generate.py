@@ -13,6 +13,13 @@ Only the last position's rows reach the final norm and the LM head.  A decode st
 no host synchronisation: the position is a host counter (prompts of a batch share one
 length), the per-sequence ``lens`` the kernel reads live on the device.  On CPU tensors
 everything runs through the ops' f32 reference paths.
+
+Ragged batches (:meth:`Generator.generate_batch`, ``prefill(lens=)``): prompts of different
+lengths are right-padded for the prefill, and the decode step then reads every position
+from ``cache.lens`` on the device (csrc/kernels/generate.hip: position-aware embedding,
+fused RoPE + K/V append at ``lens[b]``, on-device sampling with top-k / top-p and a stop
+token).  That step takes no host value that changes from token to token, so it can be
+captured once as a HIP graph and replayed (``graphs=True``).
 """
 from __future__ import annotations
 
@@ -49,10 +56,17 @@ class KVCache:
                                       for _ in range(cfg.n_layers)]
         self.lens = torch.zeros(B, device=self.device, dtype=torch.int32)
         self.pos = 0
+        # ragged: the sequences have their own lengths (prefill(lens=)): ``lens`` is then the
+        # only record of a position, ``pos`` a host upper bound of max(lens), and ``positions``
+        # (int32 [B], static so a captured step finds it) holds lens as it was when the
+        # current decode step began -- where that step's token is embedded and appended
+        self.ragged = False
+        self.positions = torch.zeros(B, device=self.device, dtype=torch.int32)
 
     def reset(self) -> None:
         self.lens.zero_()
         self.pos = 0
+        self.ragged = False
 
 
 class Generator:
@@ -129,12 +143,13 @@ class Generator:
             ops.rope_(qkv, blk.rope[0], blk.rope[1], S, cfg.n_heads, cfg.n_kv_heads, cfg.head_dim, pos_offset=pos)
         return qkv
 
-    def _head(self, h: torch.Tensor) -> torch.Tensor:
+    def _head(self, h: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Final norm + LM head of [B, D] rows -> logits [B, vocab_padded]."""
         A = self.arena
         if self.cfg.final_norm:
             h = self._norm(h, A.w("norm.weight"), A.w("norm.bias") if A.has("norm.bias") else None)
-        logits, _ = ops.linear(h, self.model.head_weight(), A.w("output.bias") if A.has("output.bias") else None)
+        logits, _ = ops.linear(h, self.model.head_weight(), A.w("output.bias") if A.has("output.bias") else None,
+                               out=out)
         return logits
 
     def _embed(self, tokens: torch.Tensor, S: int, pos: int) -> torch.Tensor:
@@ -144,13 +159,24 @@ class Generator:
 
     # ------------------------------------------------------------------ the two modes
     @torch.no_grad()
-    def prefill(self, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
+    def prefill(self, tokens: torch.Tensor, cache: KVCache, lens=None) -> torch.Tensor:
         """tokens [B, S0] -> logits [B, vocab_padded] of the last position; fills ``cache``
-        rows [0, S0) of every layer."""
+        rows [0, S0) of every layer.
+
+        With ``lens`` (host ints [B], ``1 <= lens[b] <= S0``) ``tokens`` is right-padded: row
+        b holds ``lens[b]`` tokens, then anything.  Attention is causal, so padding never
+        reaches an earlier position and the same kernels run; the logits are those of
+        position ``lens[b] - 1``.  The cache becomes ragged: ``cache.lens = lens``, cache
+        rows at and beyond ``lens[b]`` are stale (no decode step reads them), ``cache.pos``
+        is only a host upper bound of the lengths."""
         cfg = self.cfg
         B, S = tokens.shape
         if B != cache.B or S < 1 or S > cache.max_len:
             raise ValueError(f"prefill: tokens {tuple(tokens.shape)} do not fit a cache of {cache.B} x {cache.max_len}")
+        if lens is not None:
+            lens = torch.as_tensor(lens).reshape(-1).to("cpu", torch.int64)
+            if lens.numel() != B or int(lens.min()) < 1 or int(lens.max()) > S:
+                raise ValueError(f"prefill: lens must hold {B} lengths in [1, {S}]")
         H, KV, Dh = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
         x = self._embed(tokens.to(self.device), S, 0)
         for li, blk in enumerate(self.blocks):
@@ -163,14 +189,57 @@ class Generator:
             ops.attn_fwd(q, k, v, o, lse, B, S, S, H, KV, Dh, True, p_drop=0.0)
             x2, _ = ops.linear(o, blk.w("attn.wo.weight"), blk.wb("attn.wo.bias"), residual=x)
             x = self._ffn(blk, x2)
-        cache.lens.fill_(S)
         cache.pos = S
-        return self._head(x.view(B, S, -1)[:, -1].contiguous())
+        if lens is None:
+            cache.lens.fill_(S)
+            cache.ragged = False
+            return self._head(x.view(B, S, -1)[:, -1].contiguous())
+        cache.lens.copy_(lens)
+        cache.ragged = True
+        last = torch.arange(B, device=x.device) * S + (lens.to(x.device) - 1)
+        return self._head(x.index_select(0, last))
+
+    def _decode_ragged(self, tokens: torch.Tensor, cache: KVCache, active: Optional[torch.Tensor],
+                       out: Optional[torch.Tensor]) -> torch.Tensor:
+        """The decode step of a ragged cache: every position is read from ``cache.lens`` on
+        the device, so the launches and their arguments are the same at every token (the step
+        can be captured once and replayed).  ``attn_decode`` runs over ``cache.max_len`` keys'
+        worth of workgroups every step; rows past ``lens[b]`` never enter the result."""
+        cfg = self.cfg
+        B = cache.B
+        H, KV, Dh = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
+        if active is not None and (active.dtype != torch.uint8 or active.numel() != B or active.device != cache.lens.device):
+            raise ValueError("decode: active must be uint8 [B] on the cache's device")
+        cache.positions.copy_(cache.lens)          # where this token goes
+        cache.lens.add_(1 if active is None else active)      # ... and it is a key too
+        A = self.arena
+        x = ops.embed_fwd(tokens.reshape(-1), A.w("tok_embeddings.weight"),
+                          A.w("pos_embeddings.weight") if cfg.pos == "learned" else None, 1,
+                          positions=cache.positions)
+        rope = cfg.pos == "rope"
+        for li, blk in enumerate(self.blocks):
+            h1 = self._norm(x, blk.w("attn_norm.weight"), blk.wb("attn_norm.bias"))
+            qkv, _ = ops.linear(h1, blk.w("attn.wqkv.weight"), blk.wb("attn.wqkv.bias"))
+            ops.rope_kv_append(qkv, blk.rope[0] if rope else None, blk.rope[1] if rope else None, cache.k[li],
+                               cache.v[li], cache.positions, active, H, KV, Dh, rope=rope)
+            o = torch.empty(B, H * Dh, device=x.device, dtype=x.dtype)
+            ops.attn_decode(qkv[:, : H * Dh], cache.k[li], cache.v[li], cache.lens, o, H, KV, Dh,
+                            max_len=cache.max_len)
+            x2, _ = ops.linear(o, blk.w("attn.wo.weight"), blk.wb("attn.wo.bias"), residual=x)
+            x = self._ffn(blk, x2)
+        cache.pos += 1
+        return self._head(x, out=out)
 
     @torch.no_grad()
-    def decode(self, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
+    def decode(self, tokens: torch.Tensor, cache: KVCache, active: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tokens [B] (the token at position ``cache.pos`` of every sequence) -> logits
-        [B, vocab_padded] for the next position; appends one K/V row per layer."""
+        [B, vocab_padded] for the next position; appends one K/V row per layer.
+
+        On a ragged cache (``prefill(lens=)``) row b's token goes to position ``lens[b]``.
+        ``active`` (uint8 [B] on the device, ragged caches only): a row with ``active[b] ==
+        0`` keeps its cache rows and its ``lens`` entry, and its logits row is unspecified.
+        ``out``: a [B, vocab_padded] buffer for the logits."""
         cfg = self.cfg
         B, pos = cache.B, cache.pos
         if tokens.numel() != B:
@@ -179,6 +248,10 @@ class Generator:
             raise ValueError("decode: prefill the cache first")
         if pos >= cache.max_len:
             raise ValueError(f"decode: the cache is full ({cache.max_len} positions)")
+        if cache.ragged:
+            return self._decode_ragged(tokens.to(self.device), cache, active, out)
+        if active is not None:
+            raise ValueError("decode: active needs a ragged cache (prefill(lens=...))")
         H, KV, Dh = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
         cache.lens.add_(1)            # the current token is a key too
         x = self._embed(tokens.to(self.device), 1, pos)
@@ -192,7 +265,7 @@ class Generator:
             x2, _ = ops.linear(o, blk.w("attn.wo.weight"), blk.wb("attn.wo.bias"), residual=x)
             x = self._ffn(blk, x2)
         cache.pos = pos + 1
-        return self._head(x)
+        return self._head(x, out=out)
 
     # ------------------------------------------------------------------ sampling loop
     def _pick(self, logits: torch.Tensor, temperature: float, top_k: Optional[int],
@@ -237,3 +310,105 @@ class Generator:
             if i + 1 < N:
                 logits = self.decode(nxt, cache)
         return out
+
+    @torch.no_grad()
+    def generate_batch(self, prompts, max_new_tokens: int, temperature: float = 0.0, top_k: Optional[int] = None,
+                       top_p: Optional[float] = None, seed: int = 0, stop_token: Optional[int] = None,
+                       pad_token: int = 0, graphs: Optional[bool] = None):
+        """Prompts of any lengths -> ``(out, lengths)``.
+
+        ``prompts``: a list of 1-D int64 tensors (or lists of ids), each of length >= 1 with
+        ``len + max_new_tokens <= max_seq_len``.  ``out`` is ``[B, max(len) + max_new_tokens]``:
+        row b holds its prompt, then its new tokens up to and including ``stop_token``, then
+        ``pad_token``; ``lengths[b]`` (int64, on the device) counts the valid tokens.
+
+        Tokens are picked by :func:`ops.sample` (greedy at ``temperature == 0``, else
+        temperature / ``top_k`` / ``top_p`` sampling) from ``u = torch.rand(N, B)`` of a
+        generator seeded with ``seed``, drawn once up front: the same seed gives the same
+        tokens with or without graphs.  One step -- sample, record, decode -- takes no host
+        value that changes from token to token.  With ``graphs=True`` (GPU only; ``None``
+        resolves to off: measured on the MI355X, replay is not faster than the eager step at
+        B = 1 and within 1 % of it on all but one larger shape --
+        profiles/r10_generate_batch.md) the first
+        step runs eagerly, the second is captured as one HIP graph
+        (parallel/graphs.py; every allocation of the step, ``attn_decode``'s workspace
+        included, is made on the capturing stream and so comes from the graph's private pool)
+        and the rest are replays.  No host synchronisation per token: without a stop token
+        none at all, with one ``done.all()`` is read every 16th step to stop early."""
+        cfg = self.cfg
+        V, N, dev = cfg.vocab_size, int(max_new_tokens), self.device
+        rows = [torch.as_tensor(p).reshape(-1).to("cpu", torch.int64) for p in prompts]
+        if not rows or any(r.numel() < 1 for r in rows):
+            raise ValueError("generate_batch: needs at least one prompt, each of at least one token")
+        if temperature < 0 or N < 0:
+            raise ValueError("generate_batch: temperature and max_new_tokens must be >= 0")
+        lens = [int(r.numel()) for r in rows]
+        B, S0 = len(rows), max(lens)
+        if S0 + N > cfg.max_seq_len:
+            raise ValueError(f"generate_batch: {S0} prompt + {N} new tokens exceed max_seq_len = {cfg.max_seq_len} "
+                             "(the learned positions / RoPE table end there)")
+        if any(int(r.min()) < 0 or int(r.max()) >= V for r in rows):
+            raise ValueError(f"generate_batch: prompt token outside the vocabulary [0, {V})")
+        pad, stop = int(pad_token), -1 if stop_token is None else int(stop_token)
+        if not 0 <= pad < V:
+            raise ValueError(f"generate_batch: pad_token {pad} outside the vocabulary [0, {V})")
+        if stop_token is not None and not 0 <= stop < V:
+            raise ValueError(f"generate_batch: stop_token {stop} outside the vocabulary [0, {V})")
+        k = int(top_k or 0)
+        p = 1.0 if top_p is None else float(top_p)
+        if k < 0 or not 0.0 < p <= 1.0:
+            raise ValueError("generate_batch: needs top_k >= 0 and 0 < top_p <= 1")
+        use_graphs = False if graphs is None else bool(graphs)
+        if use_graphs and dev.type != "cuda":
+            raise ValueError("generate_batch: graphs need a GPU")
+
+        tokens = torch.full((B, S0), pad, dtype=torch.int64)
+        for b, r in enumerate(rows):
+            tokens[b, : lens[b]] = r
+        tokens = tokens.to(dev)
+        out = torch.full((B, S0 + N), pad, device=dev, dtype=torch.int64)
+        out[:, :S0] = tokens
+        wpos = torch.tensor(lens, device=dev, dtype=torch.int64)      # where row b's next token goes
+        if N == 0:
+            return out, wpos
+        cache = self.new_cache(B, S0 + N)
+        logits = torch.empty(B, cfg.vocab_padded, device=dev, dtype=self.dtype)
+        logits.copy_(self.prefill(tokens, cache, lens))
+        u = torch.rand(N, B, generator=torch.Generator(device=dev).manual_seed(int(seed)), device=dev)
+        # static buffers of the step
+        u_buf = torch.empty(B, device=dev, dtype=torch.float32)
+        cur = torch.empty(B, device=dev, dtype=torch.int64)
+        done = torch.zeros(B, device=dev, dtype=torch.uint8)
+        active = torch.ones(B, device=dev, dtype=torch.uint8)
+
+        def pick():
+            torch.bitwise_xor(done, 1, out=active)            # rows still running when the step begins
+            ops.sample(logits, V, u_buf, float(temperature), k, p, done, stop, pad, out=cur)
+            out.scatter_(1, wpos.unsqueeze(1), cur.unsqueeze(1))      # a finished row writes pad over pad
+            wpos.add_(active)
+
+        def step():
+            pick()
+            self.decode(cur, cache, active=active, out=logits)
+
+        gc = None
+        if use_graphs:
+            from ..parallel.graphs import GraphCache
+            gc = GraphCache("G")
+        finished = False
+        for i in range(N - 1):
+            u_buf.copy_(u[i])
+            if gc is None or i == 0:
+                step()                       # with graphs: the warm-up, and one step of progress
+            else:
+                replay = "step" in gc
+                gc.run("step", (), lambda _: step())
+                if replay:
+                    cache.pos += 1           # the captured decode counted its own step only
+            if stop >= 0 and i % 16 == 15 and bool(done.all()):
+                finished = True
+                break
+        if not finished:
+            u_buf.copy_(u[N - 1])
+            pick()
+        return out, wpos

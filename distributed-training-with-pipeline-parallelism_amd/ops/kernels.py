@@ -243,11 +243,25 @@ def xent_fwd_bwd(logits: torch.Tensor, target: torch.Tensor, vocab: int, grad_sc
 # embeddings
 # ======================================================================================
 def embed_fwd(idx: torch.Tensor, wte: torch.Tensor, wpe: Optional[torch.Tensor], S: int, pos_offset: int = 0,
-              out: Optional[torch.Tensor] = None):
+              out: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None):
+    """``positions`` (int32 [T] on wte's device): one token per sequence, row t at position
+    ``positions[t]`` read on the device (clamped to the table) instead of ``t % S +
+    pos_offset`` -- the decode step of a ragged batch (csrc/kernels/generate.hip)."""
     T = idx.numel()
     D = wte.shape[1]
     if out is None:
         out = torch.empty(T, D, device=wte.device, dtype=wte.dtype)
+    if positions is not None:
+        if positions.dtype != torch.int32 or positions.device != wte.device or positions.numel() != T:
+            raise ValueError("embed_fwd: positions must be int32 [T] on wte's device")
+        if _gpu(wte):
+            _ext().embed_pos(idx.reshape(-1), positions.reshape(-1), wte, wpe, out)
+            return out
+        e = wte.float()[idx.reshape(-1).clamp(0, wte.shape[0] - 1)]
+        if wpe is not None:
+            e = e + wpe.float()[positions.reshape(-1).long().clamp(0, wpe.shape[0] - 1)]
+        out.copy_(e.to(out.dtype))
+        return out
     if _gpu(wte):
         _ext().embed_fwd(idx.reshape(-1), wte, wpe, out, int(S), int(pos_offset))
         return out
@@ -1054,6 +1068,122 @@ def attn_decode(q, k_cache, v_cache, lens, o, H: int, Hkv: int, D: int, scale: O
         p = torch.softmax((Q @ K.transpose(-1, -2)) * scale, -1)
         o[b, : H * D].copy_((p @ V).reshape(H * D).to(o.dtype))
     return o
+
+
+# ======================================================================================
+# the ragged decode step: K/V append at a device-side position, on-device sampling
+# ======================================================================================
+def rope_kv_append(qkv: torch.Tensor, cos: Optional[torch.Tensor], sin: Optional[torch.Tensor], k_cache: torch.Tensor,
+                   v_cache: torch.Tensor, pos: torch.Tensor, active: Optional[torch.Tensor], H: int, Hkv: int, Dh: int,
+                   rope: bool = True):
+    """One new token per sequence.  qkv: packed [B, (H + 2 Hkv) * Dh] rows; pos: int32 [B] on
+    qkv's device, clamped to [0, Smax - 1]; active: uint8 [B] or None (all active).  For an
+    active row b: q is rotated in place at position pos[b] (``rope``), k is rotated and
+    written to ``k_cache[b, pos[b]]`` (the k columns of qkv keep their unrotated values), v is
+    copied to ``v_cache[b, pos[b]]``.  The rotation is :func:`rope_`'s at ``pos_offset =
+    pos[b]``, bit for bit.  An inactive row is left alone: nothing is written for it."""
+    B, Smax = qkv.shape[0], k_cache.shape[1]
+    if pos.dtype != torch.int32 or pos.device != qkv.device or pos.numel() != B:
+        raise ValueError("rope_kv_append: pos must be int32 [B] on qkv's device")
+    if active is not None and (active.dtype != torch.uint8 or active.device != qkv.device or active.numel() != B):
+        raise ValueError("rope_kv_append: active must be uint8 [B] on qkv's device")
+    if rope and (cos is None or sin is None or cos.shape[0] < Smax or sin.shape[0] < Smax):
+        raise ValueError(f"rope_kv_append: the RoPE tables need at least Smax = {Smax} rows")
+    if _gpu(qkv):
+        if Dh not in (64, 128):
+            raise ValueError(f"rope_kv_append: head_dim {Dh} is not supported by the HIP kernel (64 or 128)")
+        _ext().rope_kv_append(qkv, cos if rope else None, sin if rope else None, k_cache, v_cache, pos, active,
+                              int(H), int(Hkv), int(Dh), bool(rope))
+        return qkv
+    half = Dh // 2
+    p = pos.long().clamp(0, Smax - 1)
+    rows = torch.arange(B) if active is None else torch.nonzero(active.reshape(-1) != 0)[:, 0]
+    if rows.numel() == 0:
+        return qkv
+    x = qkv[rows].float().reshape(-1, H + 2 * Hkv, Dh)
+    if rope:
+        c, s = cos[p[rows]][:, None, :].float(), sin[p[rows]][:, None, :].float()
+        a, b = x[:, : H + Hkv, :half], x[:, : H + Hkv, half:]
+        rot = torch.cat([a * c - b * s, b * c + a * s], -1)
+    else:
+        rot = x[:, : H + Hkv]
+    if rope:
+        qkv[rows, : H * Dh] = rot[:, :H].reshape(-1, H * Dh).to(qkv.dtype)
+    k_cache[rows, p[rows], : Hkv * Dh] = rot[:, H:].reshape(-1, Hkv * Dh).to(k_cache.dtype)
+    v_cache[rows, p[rows], : Hkv * Dh] = x[:, H + Hkv:].reshape(-1, Hkv * Dh).to(v_cache.dtype)
+    return qkv
+
+
+def _sample_cpu(z: torch.Tensor, u: torch.Tensor, temperature: float, top_k: int, top_p: float) -> torch.Tensor:
+    """f32 reference of the sampling rule (csrc/kernels/generate.hip) on z = logits[:, :V]."""
+    B, V = z.shape
+    if temperature == 0:
+        return z.argmax(-1)
+    z = z / torch.tensor(temperature, dtype=torch.float32) + 0.0
+    keep = torch.ones_like(z, dtype=torch.bool)
+    if 0 < top_k < V:
+        keep = z >= z.topk(int(top_k), dim=-1).values[:, -1:]
+    w = torch.exp(z - z.max(-1, keepdim=True).values) * keep
+    if top_p < 1.0:
+        need = torch.tensor(top_p, dtype=torch.float32) * w.sum(-1)
+        for b in range(B):
+            vals, inv = torch.unique(z[b][keep[b]], return_inverse=True)         # ascending
+            mass = torch.zeros(vals.numel()).index_add_(0, inv, w[b][keep[b]])
+            above = mass.flip(0).cumsum(0).flip(0)                                 # mass of {z >= vals[i]}
+            ok = torch.nonzero(above >= need[b])[:, 0]
+            t = vals[int(ok.max())] if ok.numel() else vals[0]
+            keep[b] &= z[b] >= t
+        w = w * keep
+    c = w.cumsum(-1)
+    hit = keep & (c > (u.float() * c[:, -1])[:, None])
+    idx = torch.arange(V).expand(B, V)
+    first = torch.where(hit, idx, torch.full_like(idx, V)).min(-1).values
+    last = torch.where(keep, idx, torch.full_like(idx, -1)).max(-1).values
+    return torch.where(first < V, first, last).clamp(0, V - 1)
+
+
+def sample(logits: torch.Tensor, vocab: int, u: torch.Tensor, temperature: float = 0.0, top_k: int = 0,
+           top_p: float = 1.0, done: Optional[torch.Tensor] = None, stop_token: int = -1, pad_token: int = 0,
+           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One token id per row of ``logits`` [B, Vp] (bf16 or f32 rows, any row stride) over the
+    first ``vocab`` columns only, in f32 with z = logit / temperature:
+
+    1. ``temperature == 0``: argmax, ties to the lowest index;
+    2. ``top_k`` (0 = off): keep z >= the k-th largest z (ties at the threshold all kept);
+    3. ``top_p`` (1 = off): over the kept set, keep z >= the largest z whose upper set has
+       at least ``top_p`` of the mass (ties kept whole);
+    4. the smallest kept j whose running sum of exp(z - max), in index order, exceeds
+       ``u[b]`` times the total (``u``: f32 [B] in [0, 1)).
+
+    ``done`` (uint8 [B], optional): a row already done gets ``pad_token``; a row that emits
+    ``stop_token`` sets ``done[b]``.  Writes and returns ``out`` (int64 [B])."""
+    if logits.dim() != 2:
+        raise ValueError("sample: logits must be [B, Vp]")
+    B, Vp = logits.shape
+    vocab, top_k = int(vocab), int(top_k or 0)
+    top_p = 1.0 if top_p is None else float(top_p)
+    if not 1 <= vocab <= Vp:
+        raise ValueError(f"sample: vocab {vocab} outside [1, Vp = {Vp}]")
+    if not temperature >= 0 or top_k < 0 or not 0.0 < top_p <= 1.0:
+        raise ValueError("sample: needs temperature >= 0, top_k >= 0 and 0 < top_p <= 1")
+    if u.dtype != torch.float32 or u.device != logits.device or u.numel() != B:
+        raise ValueError("sample: u must be f32 [B] on the logits' device")
+    if done is not None and (done.dtype != torch.uint8 or done.device != logits.device or done.numel() != B):
+        raise ValueError("sample: done must be uint8 [B] on the logits' device")
+    if out is None:
+        out = torch.empty(B, device=logits.device, dtype=torch.int64)
+    elif out.dtype != torch.int64 or out.device != logits.device or out.numel() != B:
+        raise ValueError("sample: out must be int64 [B] on the logits' device")
+    if _gpu(logits):
+        _ext().sample(logits, vocab, u, float(temperature), top_k, top_p, done, int(stop_token), int(pad_token), out)
+        return out
+    tok = _sample_cpu(logits[:, :vocab].float(), u.reshape(-1), float(temperature), top_k, top_p)
+    if done is not None:
+        was = done.reshape(-1) != 0
+        tok = torch.where(was, torch.full_like(tok, int(pad_token)), tok)
+        done.reshape(-1)[(~was) & (tok == int(stop_token))] = 1
+    out.copy_(tok.reshape(out.shape))
+    return out
 
 
 # ======================================================================================

@@ -3,12 +3,19 @@
     python generate.py --checkpoint DIR --prompt "1,2,3" --max-new-tokens 16
     python generate.py --checkpoint DIR --prompt "1,2,3;7,8,9" --max-new-tokens 16 \
         --temperature 0.8 --top-k 40 --seed 1 --device cuda
+    python generate.py --checkpoint DIR --prompt "1,2,3;7,8" --max-new-tokens 16 \
+        --temperature 0.8 --top-k 40 --top-p 0.9 --stop-token 0
 
 The model configuration comes from the checkpoint's manifest; the weights are found by FQN,
 so a checkpoint written at any PP / DP degree loads into this single process.  Prompts are
 comma-separated token ids (train.py's data are ids; there is no tokenizer), several prompts
-of one shared length separated by ``;``.  Prints the prompt + generated ids, one sequence
-per line.
+separated by ``;``.  Prints the prompt + generated ids, one sequence per line.
+
+Prompts of one shared length with none of ``--top-p`` / ``--stop-token`` / ``--pad-token``
+go through ``Generator.generate``.  Prompts of different lengths, or any of those flags, go
+through ``Generator.generate_batch`` (positions and sampling on the device): each printed
+row then ends with its last valid token -- the stop token if it was produced -- and the
+padding is not printed.
 """
 from __future__ import annotations
 
@@ -20,18 +27,20 @@ def parse_prompts(text: str):
     rows = [[int(t) for t in row.replace(" ", "").split(",") if t] for row in text.split(";") if row.strip()]
     if not rows or any(not r for r in rows):
         raise ValueError("--prompt: comma-separated token ids, prompts separated by ';'")
-    if len({len(r) for r in rows}) != 1:
-        raise ValueError("--prompt: the prompts of a batch must share one length")
     return rows
 
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--checkpoint", required=True, help="directory written by save_checkpoint / train.py")
-    ap.add_argument("--prompt", required=True, help='token ids, e.g. "1,2,3" (";" between prompts)')
+    ap.add_argument("--prompt", required=True, help='token ids, e.g. "1,2,3" (";" between prompts; lengths may differ)')
     ap.add_argument("--max-new-tokens", type=int, default=16)
     ap.add_argument("--temperature", type=float, default=0.0, help="0 = greedy")
     ap.add_argument("--top-k", type=int, default=None)
+    ap.add_argument("--top-p", type=float, default=None, help="nucleus sampling: keep the smallest set of the most "
+                    "probable tokens whose mass reaches this value, in (0, 1]")
+    ap.add_argument("--stop-token", type=int, default=None, help="a sequence ends once it produces this id")
+    ap.add_argument("--pad-token", type=int, default=None, help="id that fills finished rows (default 0; not printed)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", choices=("cpu", "cuda"), default=None, help="default: cuda when available")
     a = ap.parse_args(argv)
@@ -44,6 +53,14 @@ def main(argv=None) -> int:
     bad = [t for r in rows for t in r if not 0 <= t < gen.cfg.vocab_size]
     if bad:
         raise ValueError(f"--prompt: token id {bad[0]} outside the vocabulary [0, {gen.cfg.vocab_size})")
+    ragged = len({len(r) for r in rows}) != 1
+    if ragged or a.top_p is not None or a.stop_token is not None or a.pad_token is not None:
+        out, lengths = gen.generate_batch([torch.tensor(r, dtype=torch.int64) for r in rows], a.max_new_tokens,
+                                          temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed,
+                                          stop_token=a.stop_token, pad_token=a.pad_token or 0)
+        for r, n in zip(out.tolist(), lengths.tolist()):
+            print(",".join(str(t) for t in r[:n]))
+        return 0
     out = gen.generate(torch.tensor(rows, dtype=torch.int64), a.max_new_tokens, temperature=a.temperature,
                        top_k=a.top_k, seed=a.seed)
     for r in out.tolist():
