@@ -8,6 +8,11 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <map>
+#include <optional>
+#include <string>
+
+#include "mp_gemm_plan.h"
 
 extern "C" {
 int mp_norm_fwd(int f32, int rms, const void* a, const void* b, const void* w, const void* bias, void* s_out, void* y,
@@ -93,9 +98,8 @@ int mp_set_drop_step_norm(uint64_t v, hipStream_t st);
 int mp_set_drop_step_gemm(uint64_t v, hipStream_t st);
 int mp_gemm2(const void* A, const void* B, void* C, const void* bias, const void* residual, void* aux, int M, int N,
              int K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ld_res, int64_t ld_aux, int transA, int transB,
-             int epilogue, int c_f32_accum, float alpha, int force_cfg, float* ws, float* colsum, float p_drop,
-             uint64_t seed, hipStream_t st);
-int mp_gemm2_plan(int M, int N, int K, int transA, int transB, int c_f32_accum, int force_cfg, int* split_out);
+             int epilogue, int c_f32_accum, float alpha, int cfg, int split, int force_cfg, float* ws, float* colsum,
+             float p_drop, uint64_t seed, hipStream_t st);
 int64_t mp_gemm2_ws_floats(int cfg, int split, int M, int N, int K);
 int mp_gemm2_has_probe_engines();
 int mp_gemm_tt_grouped(int n, const void* const* A, const void* const* B, float* const* C, const int* M, const int* N,
@@ -799,8 +803,25 @@ void gemm(torch::Tensor A, torch::Tensor B, torch::Tensor C, c10::optional<torch
         "gemm");
 }
 
-// v2 engine (8 waves, glds staging).  Returns false if the combination is not provided
-// by v2 (the caller then uses gemm()).
+// What the v2 GEMM will run (mp_gemm_plan.h).  env: the planner switches by name over their
+// defaults; none: the process environment, read once.
+using PlanEnvDict = std::map<std::string, std::string>;
+g2::Plan gemm2_plan(int64_t M, int64_t N, int64_t K, bool transA, bool transB, bool accum, int64_t force_cfg,
+                    const std::optional<PlanEnvDict>& env) {
+  g2::PlanEnv parsed;
+  if (env.has_value()) {
+    for (const auto& kv : *env)
+      TORCH_CHECK(g2::PlanEnv::known(kv.first.c_str()), "gemm2_plan: ", kv.first, " is not a planner switch");
+    parsed = g2::PlanEnv::parse([&](const char* name) {
+      const auto it = env->find(name);
+      return it == env->end() ? (const char*)nullptr : it->second.c_str();
+    });
+  }
+  return g2::plan_gemm((int)M, (int)N, (int)K, transA, transB, accum, (int)force_cfg,
+                       env.has_value() ? parsed : g2::PlanEnv::process(), mp_gemm2_has_probe_engines() != 0);
+}
+
+// v2 engine (8 waves, glds staging).
 // returns 1 if done, 0 if the combination is not provided by v2 (caller uses gemm()),
 // 2 if done WITHOUT the requested fused column sums (caller sums separately)
 int64_t gemm2(torch::Tensor A, torch::Tensor B, torch::Tensor C, c10::optional<torch::Tensor> bias,
@@ -821,36 +842,27 @@ int64_t gemm2(torch::Tensor A, torch::Tensor B, torch::Tensor C, c10::optional<t
     // the mask index is row * ldc + column: act_fwd / act_bwd regenerate it for a contiguous output
     TORCH_CHECK(C.is_contiguous(), "gemm2: p_drop needs a contiguous C");
   }
-  // split-K slabs (plain stores + one reduce pass instead of f32 atomics)
   // split-K slabs (plain stores + one reduce pass instead of f32 atomics), or the stream-K
   // engine's flags + partial tiles: from the caching allocator on the current stream (graph
   // captures take it from their private pool), so concurrent streams never share one
-  int split = 1;
-  const int cfg = mp_gemm2_plan(M, N, K, transA, transB, accum, (int)force_cfg, &split);
+  const g2::Plan plan = gemm2_plan(M, N, K, transA, transB, accum, force_cfg, std::nullopt);
   torch::Tensor ws;
-  const int64_t ws_n = mp_gemm2_ws_floats(cfg, split, M, N, K);
+  const int64_t ws_n = mp_gemm2_ws_floats(plan.cfg, plan.split, M, N, K);
   if (ws_n > 0) ws = torch::empty({ws_n}, C.options().dtype(torch::kFloat32));
-  const int rc = mp_gemm2(A.data_ptr(), B.data_ptr(), C.data_ptr(), ptr_or_null(bias), ptr_or_null(residual),
-                          mptr_or_null(aux), M, N, K, A.stride(0), B.stride(0), C.stride(0),
-                          residual.has_value() ? residual->stride(0) : 0, aux.has_value() ? aux->stride(0) : 0,
-                          transA, transB, epilogue, accum, (float)alpha, (int)force_cfg,
-                          ws.defined() ? ws.data_ptr<float>() : nullptr,
-                          colsum.has_value() ? colsum->data_ptr<float>() : nullptr, (float)p_drop, (uint64_t)seed,
-                          cur_stream());
-  if (rc == -3) {
-    const int rc2 = mp_gemm2(A.data_ptr(), B.data_ptr(), C.data_ptr(), ptr_or_null(bias), ptr_or_null(residual),
-                             mptr_or_null(aux), M, N, K, A.stride(0), B.stride(0), C.stride(0),
-                             residual.has_value() ? residual->stride(0) : 0, aux.has_value() ? aux->stride(0) : 0,
-                             transA, transB, epilogue, accum, (float)alpha, (int)force_cfg,
-                             ws.defined() ? ws.data_ptr<float>() : nullptr, nullptr, (float)p_drop, (uint64_t)seed,
-                             cur_stream());
-    if (rc2 == -2 || rc2 == -1) return 0;
-    check(rc2, "gemm2");
-    return 2;
-  }
+  const auto run = [&](float* colsum_ptr) {
+    return mp_gemm2(A.data_ptr(), B.data_ptr(), C.data_ptr(), ptr_or_null(bias), ptr_or_null(residual),
+                    mptr_or_null(aux), M, N, K, A.stride(0), B.stride(0), C.stride(0),
+                    residual.has_value() ? residual->stride(0) : 0, aux.has_value() ? aux->stride(0) : 0, transA,
+                    transB, epilogue, accum, (float)alpha, plan.cfg, plan.split, (int)force_cfg,
+                    ws.defined() ? ws.data_ptr<float>() : nullptr, colsum_ptr, (float)p_drop, (uint64_t)seed,
+                    cur_stream());
+  };
+  int rc = run(colsum.has_value() ? colsum->data_ptr<float>() : nullptr);
+  const bool no_colsum = rc == -3;
+  if (no_colsum) rc = run(nullptr);
   if (rc == -2 || rc == -1) return 0;
   check(rc, "gemm2");
-  return 1;
+  return no_colsum ? 2 : 1;
 }
 
 // grouped weight-gradient GEMMs: C[i] (f32 [N_i, K_i]) += alpha * dy[i]^T x[i]
@@ -1166,11 +1178,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("result"), pybind11::arg("waiter") = 0);
   m.def("probe_set", &probe_set, pybind11::arg("flag"), pybind11::arg("value"), pybind11::arg("setter") = 0);
   m.def("probe_clock_khz", []() { return mp_probe_clock_khz(); });
-  m.def("gemm2_plan", [](int64_t M, int64_t N, int64_t K, bool transA, bool transB, bool accum, int64_t force_cfg) {
-    int split = 1;
-    const int cfg = mp_gemm2_plan((int)M, (int)N, (int)K, transA, transB, accum, (int)force_cfg, &split);
-    return std::make_tuple(cfg, split);
-  }, "engine config + split-K factor the v2 GEMM picks (14: stream-K gemm7)");
+  m.def("gemm2_plan", [](int64_t M, int64_t N, int64_t K, bool transA, bool transB, bool accum, int64_t force_cfg,
+                         std::optional<PlanEnvDict> env) {
+    const g2::Plan p = gemm2_plan(M, N, K, transA, transB, accum, force_cfg, env);
+    return std::make_tuple(p.cfg, p.split);
+  }, pybind11::arg("M"), pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("transA"), pybind11::arg("transB"),
+     pybind11::arg("accum"), pybind11::arg("force_cfg"), pybind11::arg("env") = pybind11::none(),
+     "engine config + split-K factor the v2 GEMM picks (14: stream-K gemm7); env: the MIPIPE_* planner "
+     "switches as a dict over their defaults instead of the process environment");
   m.def("gemm_f32_plan", [](int64_t M, int64_t N, int64_t K, int64_t force_ks) {
     int split = 1, sk_grid = 0, sk_chunk = 0;
     const int big = mp_gemm_f32_plan((int)M, (int)N, (int)K, (int)force_ks, &split, &sk_grid, &sk_chunk);

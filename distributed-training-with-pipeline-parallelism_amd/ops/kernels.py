@@ -657,7 +657,7 @@ _GROUP3_MIN_T = 16384
 class DW:
     """A weight-gradient job ``dw (f32) += alpha * dy^T x`` kept as data, so that
     :func:`run_wjobs` can issue the short-token ones of a job list as ONE grouped launch
-    (csrc/kernels/gemm2.hip ``gemms_tt_grouped_kernel``) and the long-token ones as one
+    (csrc/include/mp_gemm_small.h ``gemms_tt_grouped_kernel``) and the long-token ones as one
     grouped 256x256 split-K launch (``gemm3_tt_grouped_kernel``).  Calling it runs it alone."""
     __slots__ = ("dy", "x", "dw", "alpha")
 
@@ -683,7 +683,7 @@ class DW:
 
     def groupable(self) -> bool:
         """Short reductions (<= 4096 tokens) over few 256x256 output tiles: the shapes the
-        planner sends to the small 64x64 TT engine (gemm2.hip mp_gemm2_plan, cfg 13)."""
+        planner sends to the small 64x64 TT engine (mp_gemm_plan.h plan_tt, cfg 13)."""
         return self._tt_operands() and self.dy.shape[0] <= 4096 and self.tiles256() < 64
 
     def groupable3(self) -> bool:

@@ -1,4 +1,4 @@
-"""float64 reference of the GEMM engines (gemm.hip, gemm2.hip, gemm_f32.hip), the componentwise
+"""float64 reference of the GEMM engines (gemm.hip, gemm2.hip + mp_gemm_*.h, gemm_f32.hip), the componentwise
 error scale of every output, the check the GPU edge tests run, and the cases they use.
 
 Plain functions: no ``ops`` import.  ``gemm_ref`` takes the tensors the kernel sees (views with

@@ -1,10 +1,11 @@
-"""Edge cases of the GEMM engines (gemm.hip, gemm2.hip, gemm_f32.hip) against the float64
-reference of gemm_refs.py (itself checked on the CPU in test_gemm_refs_cpu.py, together with
-the teeth of the error metric used here).
+"""Edge cases of the GEMM engines (gemm.hip; gemm2.hip with its engines in
+csrc/include/mp_gemm_*.h; gemm_f32.hip) against the float64 reference of gemm_refs.py (itself
+checked on the CPU in test_gemm_refs_cpu.py, together with the teeth of the error metric used
+here).
 
 The cases (gemm_refs.CASES / F32_CASES) are the smallest shapes that reach each engine and each
 ragged edge; the launcher branch is the last part of a case id: cfg<k>.s<split> exactly as the
-binding ``gemm2_plan`` reports it for the case (asserted, so a planner change fails the case
+binding ``gemm2_plan`` (mp_gemm_plan.h) reports it for the case (asserted, so a planner change fails the case
 instead of silently moving the coverage), v1 (the fallback for M % 8 != 0: gemm2 must refuse
 the call), f32.64 / f32.128 (+ .s<split>) and f32.sk as ``gemm_f32_plan`` reports them.
 
