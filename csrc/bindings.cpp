@@ -54,8 +54,8 @@ int mp_rope(void* qkv, const float* cs, const float* sn, int T, int S, int H, in
 int mp_embed_pos(const int64_t* idx, const int* pos, const void* wte, const void* wpe, void* out, int B, int D,
                  int n_tok, int n_pos, int f32, hipStream_t st);
 int mp_rope_kv_append(void* qkv, const float* cs, const float* sn, void* kc, void* vc, const int* pos,
-                      const uint8_t* active, int B, int H, int Hkv, int Dh, int Smax, int64_t qkv_ld, int64_t k_bs,
-                      int64_t k_ts, int64_t v_bs, int64_t v_ts, int rope, hipStream_t st);
+                      const uint8_t* active, const int* counts, int B, int T, int H, int Hkv, int Dh, int Smax,
+                      int64_t qkv_ld, int64_t k_bs, int64_t k_ts, int64_t v_bs, int64_t v_ts, int rope, hipStream_t st);
 int mp_sample(const void* logits, int64_t ld, const float* u, uint8_t* done, int64_t* out, int B, int V, int Vp,
               float temperature, int top_k, float top_p, int stop_token, int pad_token, int f32, hipStream_t st);
 int mp_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int Sq, int Sk, int H,
@@ -79,6 +79,11 @@ int mp_attn_decode(const void* q, const void* k, const void* v, const int* lens,
                    int64_t v_ts, int64_t o_stride, float scale, int splits, hipStream_t st);
 int mp_attn_decode_plan(int B, int Hkv, int max_len);
 int64_t mp_attn_decode_ws_floats(int B, int H, int D, int splits);
+int mp_attn_append(const void* q, const void* k, const void* v, const int* base, const int* counts, void* o, float* ws,
+                   int B, int T, int H, int Hkv, int D, int Smax, int max_len, int64_t q_stride, int64_t k_bs,
+                   int64_t k_ts, int64_t v_bs, int64_t v_ts, int64_t o_stride, float scale, int splits, hipStream_t st);
+int mp_attn_append_plan(int B, int T, int Hkv, int rep, int max_len);
+int64_t mp_attn_append_ws_floats(int B, int T, int H, int D, int splits);
 int mp_attn_f32_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int Sq, int Sk, int H,
                     int Hkv, int D, int64_t qs, int64_t ks, int64_t vs, int64_t os, int causal, float scale,
                     float p_drop, uint64_t seed, hipStream_t st);
@@ -620,6 +625,59 @@ int64_t attn_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cach
   return ns;
 }
 
+// Append attention (attention_append.hip): T new tokens per sequence, already in the cache at
+// rows base[b] + t, each attending causally over the cache.  q/o: [B*T, H*D] row views;
+// base: int32 [B] on the device (valid rows before the call); counts: int32 [B] (optional,
+// real tokens per sequence); max_len >= max(base + counts) sizes the grid.  Returns the split
+// count used.
+int64_t attn_append(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor base,
+                    c10::optional<torch::Tensor> counts, torch::Tensor o, int64_t T, int64_t H, int64_t Hkv, int64_t D,
+                    int64_t max_len, double scale, int64_t splits) {
+  req(base, torch::kInt32, "base");
+  if (counts.has_value()) req(*counts, torch::kInt32, "counts");
+  for (const torch::Tensor* t : {&q, &k_cache, &v_cache, &o})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16, "attn_append: q/k_cache/v_cache/o must be bf16 GPU tensors");
+  TORCH_CHECK(q.dim() == 2 && o.dim() == 2 && q.stride(1) == 1 && o.stride(1) == 1, "attn_append: q/o are [B*T, H*D] rows");
+  TORCH_CHECK(k_cache.dim() == 3 && v_cache.dim() == 3 && k_cache.stride(2) == 1 && v_cache.stride(2) == 1,
+              "attn_append: caches are [B, Smax, Hkv*D] with a unit inner stride");
+  const int64_t B = k_cache.size(0), Smax = k_cache.size(1);
+  TORCH_CHECK(D == 64 || D == 128, "attn_append: head_dim ", D, " is not supported (64 or 128)");
+  TORCH_CHECK(Hkv >= 1 && H >= 1 && H % Hkv == 0 && H / Hkv <= 8,
+              "attn_append: H = ", H, ", Hkv = ", Hkv, " is not supported (H % Hkv == 0, H / Hkv <= 8)");
+  TORCH_CHECK(T >= 1 && B >= 1 && B * T <= INT_MAX && q.size(0) == B * T && o.size(0) == B * T,
+              "attn_append: q/o must hold B * T = ", B * T, " rows");
+  TORCH_CHECK(q.size(1) == H * D && o.size(1) == H * D, "attn_append: q/o shape");
+  TORCH_CHECK(v_cache.size(0) == B && v_cache.size(1) == Smax && k_cache.size(2) == Hkv * D &&
+                  v_cache.size(2) == Hkv * D, "attn_append: cache shape");
+  TORCH_CHECK(base.is_contiguous() && base.numel() == B, "attn_append: base must hold one length per sequence");
+  for (const torch::Tensor* t : {&k_cache, &v_cache, &o, &base})
+    TORCH_CHECK(t->get_device() == q.get_device(), "attn_append: every tensor must be on q's GPU");
+  TORCH_CHECK(!counts.has_value() || counts->get_device() == q.get_device(), "attn_append: counts must be on q's GPU");
+  TORCH_CHECK(!counts.has_value() || (counts->is_contiguous() && counts->numel() == B),
+              "attn_append: counts must hold one count per sequence");
+  TORCH_CHECK(max_len >= 1 && max_len <= Smax, "attn_append: max_len ", max_len, " outside [1, ", Smax, "]");
+  TORCH_CHECK(splits >= 0 && splits <= max_len && splits <= 256, "attn_append: splits ", splits,
+              " outside [0, min(max_len, 256)]");
+  const int64_t rep = H / Hkv;
+  TORCH_CHECK(B * ((T * rep + 31) / 32) <= 65535 && Hkv <= 65535 && H <= 65535,
+              "attn_append: batch x query tiles / heads exceed the grid");
+  const auto aligned = [](const torch::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; };
+  TORCH_CHECK(aligned(q) && aligned(k_cache) && aligned(v_cache) && q.stride(0) % 8 == 0 &&
+                  k_cache.stride(0) % 8 == 0 && k_cache.stride(1) % 8 == 0 && v_cache.stride(0) % 8 == 0 &&
+                  v_cache.stride(1) % 8 == 0,
+              "attn_append: q / cache rows must be 16-byte aligned");
+  const int ns = splits > 0 ? (int)splits : mp_attn_append_plan((int)B, (int)T, (int)Hkv, (int)rep, (int)max_len);
+  torch::Tensor ws = torch::empty({mp_attn_append_ws_floats((int)B, (int)T, (int)H, (int)D, ns)},
+                                  q.options().dtype(torch::kFloat32));
+  check(mp_attn_append(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), base.data_ptr<int>(),
+                       counts.has_value() ? counts->data_ptr<int>() : nullptr, o.data_ptr(), ws.data_ptr<float>(),
+                       (int)B, (int)T, (int)H, (int)Hkv, (int)D, (int)Smax, (int)max_len, q.stride(0),
+                       k_cache.stride(0), k_cache.stride(1), v_cache.stride(0), v_cache.stride(1), o.stride(0),
+                       (float)scale, ns, cur_stream()),
+        "attn_append");
+  return ns;
+}
+
 // ---- the ragged decode step (generate.hip): every position is read from device memory
 // a contiguous [B] vector of dtype dt on `ref`'s GPU (pos, active, u, done, out)
 void gen_vec(const char* fn, const char* name, const torch::Tensor& t, torch::ScalarType dt, int64_t B,
@@ -659,12 +717,14 @@ void embed_pos(torch::Tensor idx, torch::Tensor pos, torch::Tensor wte, c10::opt
         "embed_pos");
 }
 
-// qkv: [B, (H + 2 Hkv) Dh] rows (one token per sequence); caches: [B, Smax, Hkv * Dh] views;
-// pos: int32 [B]; active: uint8 [B] (optional).  The RoPE tables must cover every position
-// the clamp can produce: Smax rows.
+// qkv: [B * T, (H + 2 Hkv) Dh] rows (T tokens per sequence, row b * T + t at position
+// pos[b] + t); caches: [B, Smax, Hkv * Dh] views; pos: int32 [B]; active: uint8 [B]
+// (optional); counts: int32 [B] (optional: only rows t < counts[b] are touched).  The RoPE
+// tables must cover every position the clamp can produce: Smax rows.
 void rope_kv_append(torch::Tensor qkv, c10::optional<torch::Tensor> cs, c10::optional<torch::Tensor> sn,
                     torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor pos,
-                    c10::optional<torch::Tensor> active, int64_t H, int64_t Hkv, int64_t Dh, bool rope) {
+                    c10::optional<torch::Tensor> active, int64_t H, int64_t Hkv, int64_t Dh, bool rope, int64_t T,
+                    c10::optional<torch::Tensor> counts) {
   const char* fn = "rope_kv_append";
   TORCH_CHECK(Dh == 64 || Dh == 128, fn, ": head_dim ", Dh, " is not supported (64 or 128)");
   TORCH_CHECK(H >= 1 && Hkv >= 1 && H <= 65535 && Hkv <= 65535, fn, ": bad head counts");
@@ -675,22 +735,24 @@ void rope_kv_append(torch::Tensor qkv, c10::optional<torch::Tensor> cs, c10::opt
   }
   const int64_t width = (H + 2 * Hkv) * Dh;
   TORCH_CHECK(qkv.dim() == 2 && qkv.size(1) == width && qkv.stride(1) == 1, fn, ": qkv must be [B, (H + 2 Hkv) Dh] rows");
-  const int64_t B = qkv.size(0);
+  TORCH_CHECK(T >= 1 && qkv.size(0) >= T && qkv.size(0) % T == 0 && qkv.size(0) <= INT_MAX, fn, ": qkv must hold B * T rows");
+  const int64_t B = qkv.size(0) / T, rows = qkv.size(0);
   TORCH_CHECK(B >= 1 && B <= 65535, fn, ": batch outside [1, 65535]");
   TORCH_CHECK(k_cache.dim() == 3 && v_cache.dim() == 3 && k_cache.stride(2) == 1 && v_cache.stride(2) == 1,
               fn, ": caches are [B, Smax, Hkv*Dh] with a unit inner stride");
   const int64_t Smax = k_cache.size(1);
   TORCH_CHECK(k_cache.size(0) == B && v_cache.size(0) == B && v_cache.size(1) == Smax && Smax >= 1 &&
                   Smax <= INT_MAX && k_cache.size(2) == Hkv * Dh && v_cache.size(2) == Hkv * Dh, fn, ": cache shape");
-  TORCH_CHECK(gen_aligned(qkv) && gen_aligned(k_cache) && gen_aligned(v_cache) && (B == 1 || qkv.stride(0) % 8 == 0) &&
+  TORCH_CHECK(gen_aligned(qkv) && gen_aligned(k_cache) && gen_aligned(v_cache) && (rows == 1 || qkv.stride(0) % 8 == 0) &&
                   k_cache.stride(0) % 8 == 0 && k_cache.stride(1) % 8 == 0 && v_cache.stride(0) % 8 == 0 &&
                   v_cache.stride(1) % 8 == 0, fn, ": qkv / cache rows must be 16-byte aligned");
-  TORCH_CHECK(B == 1 || qkv.stride(0) >= width, fn, ": qkv rows overlap");
+  TORCH_CHECK(rows == 1 || qkv.stride(0) >= width, fn, ": qkv rows overlap");
   TORCH_CHECK(k_cache.stride(1) >= Hkv * Dh && v_cache.stride(1) >= Hkv * Dh &&
                   (B == 1 || (k_cache.stride(0) >= Smax * k_cache.stride(1) && v_cache.stride(0) >= Smax * v_cache.stride(1))),
               fn, ": cache rows overlap");
   gen_vec(fn, "pos", pos, torch::kInt32, B, qkv);
   if (active.has_value()) gen_vec(fn, "active", *active, torch::kUInt8, B, qkv);
+  if (counts.has_value()) gen_vec(fn, "counts", *counts, torch::kInt32, B, qkv);
   const float* cp = nullptr;
   const float* sp = nullptr;
   if (rope) {
@@ -705,7 +767,8 @@ void rope_kv_append(torch::Tensor qkv, c10::optional<torch::Tensor> cs, c10::opt
     sp = sn->data_ptr<float>();
   }
   check(mp_rope_kv_append(qkv.data_ptr(), cp, sp, k_cache.data_ptr(), v_cache.data_ptr(), pos.data_ptr<int>(),
-                          active.has_value() ? active->data_ptr<uint8_t>() : nullptr, (int)B, (int)H, (int)Hkv,
+                          active.has_value() ? active->data_ptr<uint8_t>() : nullptr,
+                          counts.has_value() ? counts->data_ptr<int>() : nullptr, (int)B, (int)T, (int)H, (int)Hkv,
                           (int)Dh, (int)Smax, qkv.stride(0), k_cache.stride(0), k_cache.stride(1), v_cache.stride(0),
                           v_cache.stride(1), rope ? 1 : 0, cur_stream()),
         fn);
@@ -1158,7 +1221,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return mp_attn_decode_plan((int)B, (int)Hkv, (int)max_len);
   }, "key splits the decode attention picks for B sequences x Hkv KV heads over max_len keys");
   m.def("embed_pos", &embed_pos);
-  m.def("rope_kv_append", &rope_kv_append);
+  m.def("attn_append", &attn_append, pybind11::arg("q"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
+        pybind11::arg("base"), pybind11::arg("counts"), pybind11::arg("o"), pybind11::arg("T"), pybind11::arg("H"),
+        pybind11::arg("Hkv"), pybind11::arg("D"), pybind11::arg("max_len"), pybind11::arg("scale"),
+        pybind11::arg("splits") = 0);
+  m.def("attn_append_plan", [](int64_t B, int64_t T, int64_t Hkv, int64_t rep, int64_t max_len) {
+    return mp_attn_append_plan((int)B, (int)T, (int)Hkv, (int)rep, (int)max_len);
+  }, "key splits the append attention picks for B sequences x T tokens x Hkv KV heads of rep query heads over max_len keys");
+  m.def("rope_kv_append", &rope_kv_append, pybind11::arg("qkv"), pybind11::arg("cos"), pybind11::arg("sin"),
+        pybind11::arg("k_cache"), pybind11::arg("v_cache"), pybind11::arg("pos"), pybind11::arg("active"),
+        pybind11::arg("H"), pybind11::arg("Hkv"), pybind11::arg("Dh"), pybind11::arg("rope"), pybind11::arg("T") = 1,
+        pybind11::arg("counts") = pybind11::none());
   m.def("sample", &sample);
   m.def("gemm", &gemm);
   m.def("lane_merge", &lane_merge, pybind11::arg("g0"), pybind11::arg("lanes"), pybind11::arg("sumsq") = pybind11::none());

@@ -14,15 +14,15 @@
 //     has no cross-slot traffic.  The slots of a wave are merged with shuffles and the four
 //     waves through LDS once, at the end of the chunk.  The workgroup writes its
 //     unnormalised f32 output [D] and its (max, sum) per query head into the workspace.
-//  2. attn_decode_combine, grid (H, B), D threads: merges the splits in split order and
-//     writes bf16.  No atomics anywhere: results are bit-identical from run to run.
+//  2. attn_split_combine (mp_attn_split.h), grid (H, B), D threads: merges the splits in split
+//     order and writes bf16.  No atomics anywhere: results are bit-identical from run to run.
 //
 // A split that lies wholly beyond lens[b] writes (-inf, 0) and a zero row, which the
 // combine ignores.  Keys at positions >= lens[b] never enter a result: a lane whose key
 // index is past the end re-reads the chunk's last valid row (an address that is always
 // inside the valid part of the cache) and its score is set to -inf, so its weight is an
 // exact zero whatever the stale cache rows hold.
-#include "mp_common.h"
+#include "mp_attn_split.h"
 
 using namespace mp;
 
@@ -37,7 +37,7 @@ constexpr int kUnroll = 4;                           // K and V loads in flight 
 constexpr int kDecodeMinChunk = 256;
 constexpr int kDecodeCUs = 256;
 constexpr int kDecodeWgPerCU = 2;
-constexpr int kDecodeMaxSplits = 256;
+constexpr int kDecodeMaxSplits = kSplitMaxSplits;
 
 __device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
 
@@ -208,34 +208,6 @@ __global__ __launch_bounds__(kDecodeThreads) void attn_decode_partial(
   }
 }
 
-// out[b, h, :] = sum_s o_s 2^(m_s - M) / sum_s l_s 2^(m_s - M), splits in index order
-template <int D>
-__global__ __launch_bounds__(D) void attn_decode_combine(const float* __restrict__ part_o,
-                                                         const float* __restrict__ part_ml, bf16_t* __restrict__ o,
-                                                         int H, int nsplit, int64_t o_stride) {
-  const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
-  const int64_t row0 = ((int64_t)b * H + h) * nsplit;
-  // the splits' (max, sum) pairs: loaded side by side, not one round trip per split
-  __shared__ float sh_m[kDecodeMaxSplits], sh_w[kDecodeMaxSplits];
-  for (int s = d; s < nsplit; s += D) {
-    sh_m[s] = part_ml[(row0 + s) * 2];
-    sh_w[s] = part_ml[(row0 + s) * 2 + 1];
-  }
-  __syncthreads();
-  float M = -INFINITY;
-  for (int s = 0; s < nsplit; ++s) M = fmaxf(M, sh_m[s]);
-  const float ms = M == -INFINITY ? 0.f : M;
-  // every thread sums in split order; an empty split, (-inf, 0) with a zero row, has weight 0
-  float L = 0.f, O = 0.f;
-#pragma unroll 8
-  for (int s = 0; s < nsplit; ++s) {
-    const float sc = exp2_fast(sh_m[s] - ms);
-    L += sh_w[s] * sc;
-    O += part_o[(row0 + s) * D + d] * sc;
-  }
-  o[(int64_t)b * o_stride + (int64_t)h * D + d] = f2bf(L > 0.f ? O / L : 0.f);
-}
-
 template <int D, int REP>
 int launch(const void* q, const void* k, const void* v, const int* lens, void* o, float* ws, int B, int H, int Hkv,
            int Smax, int max_len, int64_t q_stride, int64_t k_bs, int64_t k_ts, int64_t v_bs, int64_t v_ts,
@@ -247,7 +219,8 @@ int launch(const void* q, const void* k, const void* v, const int* lens, void* o
   attn_decode_partial<D, REP><<<dim3(splits, Hkv, B), kDecodeThreads, 0, st>>>(
       (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, lens, part_o, part_ml, H, rep, Smax, chunk, q_stride, k_bs,
       k_ts, v_bs, v_ts, scale * 1.4426950408889634f);
-  attn_decode_combine<D><<<dim3(H, B), D, 0, st>>>(part_o, part_ml, (bf16_t*)o, H, splits, o_stride);
+  attn_split_combine<D><<<attn_split_combine_grid(B, H), D, 0, st>>>(part_o, part_ml, (bf16_t*)o, B, H, splits,
+                                                                      o_stride);
   return (int)hipGetLastError();
 }
 

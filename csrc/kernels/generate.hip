@@ -4,12 +4,13 @@
 //
 //   embed_pos       out[b, :] = wte[idx[b], :] (+ wpe[pos[b], :]): embed_fwd at S = 1 with a
 //                   per-row device position.  One wave per row, 16-byte vectors.
-//   rope_kv_append  per sequence b of a packed [B, (H + 2 Hkv) Dh] qkv row: q rotated in place
-//                   at pos[b] (rope_rot4 of mp_rope.h, the arithmetic of rope_kernel, so the
-//                   bits are those of rope at pos_offset = pos[b]); k rotated into
-//                   k_cache[b, pos[b], :] (the qkv row keeps the unrotated k); v copied to
-//                   v_cache[b, pos[b], :].  rope = 0: the two appends alone.  A row with
-//                   active[b] == 0 is left alone altogether.  One thread per 16-byte vector
+//   rope_kv_append  per row b * T + t (new token t of sequence b) of packed
+//                   [B * T, (H + 2 Hkv) Dh] qkv rows, at p = pos[b] + t: q rotated in place
+//                   at p (rope_rot4 of mp_rope.h, the arithmetic of rope_kernel, so the
+//                   bits are those of rope at pos_offset = p); k rotated into
+//                   k_cache[b, p, :] (the qkv row keeps the unrotated k); v copied to
+//                   v_cache[b, p, :].  rope = 0: the two appends alone.  A row with
+//                   active[b] == 0 or t >= counts[b] is left alone altogether.  One thread per 16-byte vector
 //                   (rotations: a 16-byte vector of each half); replaces one rope and two
 //                   copy launches per layer.
 //   sample          one 1024-thread workgroup per row of logits [B, Vp] (bf16 or f32, row
@@ -93,21 +94,25 @@ extern "C" int mp_embed_pos(const int64_t* idx, const int* pos, const void* wte,
 __global__ void __launch_bounds__(256) rope_kv_append_kernel(bf16_t* __restrict__ qkv, const float* __restrict__ cs,
                                                              const float* __restrict__ sn, bf16_t* __restrict__ kc,
                                                              bf16_t* __restrict__ vc, const int* __restrict__ pos,
-                                                             const uint8_t* __restrict__ active, int H, int Hkv,
+                                                             const uint8_t* __restrict__ active,
+                                                             const int* __restrict__ counts, int T, int H, int Hkv,
                                                              int Dh, int Smax, int64_t qkv_ld, int64_t k_bs,
                                                              int64_t k_ts, int64_t v_bs, int64_t v_ts, int rope) {
-  const int b = blockIdx.y;
+  const int n = blockIdx.x;                  // row b * T + t: new token t of sequence b
+  const int b = n / T, t = n % T;
   if (active && !active[b]) return;
+  if (counts && t >= counts[b]) return;
   int p = pos[b];
   p = p < 0 ? 0 : (p >= Smax ? Smax - 1 : p);
+  p = min(p + t, Smax - 1);
   const int half = Dh / 2, h8 = half / 8;
-  bf16_t* row = qkv + (int64_t)b * qkv_ld;
+  bf16_t* row = qkv + (int64_t)n * qkv_ld;
   bf16_t* krow = kc + (int64_t)b * k_bs + (int64_t)p * k_ts;
   bf16_t* vrow = vc + (int64_t)b * v_bs + (int64_t)p * v_ts;
   const int n_rot = rope ? (H + Hkv) * h8 : 0;
   const int n_kcopy = rope ? 0 : Hkv * 2 * h8;
   const int n_vcopy = Hkv * 2 * h8;
-  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int i = blockIdx.y * 256 + threadIdx.x;
   if (i < n_rot) {
     const int h = i / h8, v8 = i % h8;       // h < H: a q head, else k head h - H
     const bf16_t* src = row + (int64_t)h * Dh + v8 * 8;
@@ -135,15 +140,17 @@ __global__ void __launch_bounds__(256) rope_kv_append_kernel(bf16_t* __restrict_
 }
 
 extern "C" int mp_rope_kv_append(void* qkv, const float* cs, const float* sn, void* kc, void* vc, const int* pos,
-                                 const uint8_t* active, int B, int H, int Hkv, int Dh, int Smax, int64_t qkv_ld,
-                                 int64_t k_bs, int64_t k_ts, int64_t v_bs, int64_t v_ts, int rope, hipStream_t st) {
-  if ((Dh != 64 && Dh != 128) || B < 1 || B > 65535 || H < 1 || Hkv < 1 || Smax < 1) return -1;
+                                 const uint8_t* active, const int* counts, int B, int T, int H, int Hkv, int Dh,
+                                 int Smax, int64_t qkv_ld, int64_t k_bs, int64_t k_ts, int64_t v_bs, int64_t v_ts,
+                                 int rope, hipStream_t st) {
+  if ((Dh != 64 && Dh != 128) || B < 1 || T < 1 || (int64_t)B * T > INT_MAX || H < 1 || Hkv < 1 || Smax < 1) return -1;
   if (rope && (!cs || !sn)) return -1;
   const int h8 = Dh / 16;
   const int items = rope ? (H + Hkv) * h8 + Hkv * 2 * h8 : 2 * Hkv * 2 * h8;
-  dim3 grid((items + 255) / 256, B);
-  rope_kv_append_kernel<<<grid, 256, 0, st>>>((bf16_t*)qkv, cs, sn, (bf16_t*)kc, (bf16_t*)vc, pos, active, H, Hkv, Dh,
-                                              Smax, qkv_ld, k_bs, k_ts, v_bs, v_ts, rope);
+  if ((items + 255) / 256 > 65535) return -1;
+  dim3 grid(B * T, (items + 255) / 256);
+  rope_kv_append_kernel<<<grid, 256, 0, st>>>((bf16_t*)qkv, cs, sn, (bf16_t*)kc, (bf16_t*)vc, pos, active, counts, T, H,
+                                              Hkv, Dh, Smax, qkv_ld, k_bs, k_ts, v_bs, v_ts, rope);
   return (int)hipGetLastError();
 }
 

@@ -20,6 +20,13 @@ from ``cache.lens`` on the device (csrc/kernels/generate.hip: position-aware emb
 fused RoPE + K/V append at ``lens[b]``, on-device sampling with top-k / top-p and a stop
 token).  That step takes no host value that changes from token to token, so it can be
 captured once as a HIP graph and replayed (``graphs=True``).
+
+Several tokens at once (:meth:`Generator.extend`): ``T`` new tokens per sequence are appended
+at ``cache.lens[b] ...`` and attend causally over the cache plus the earlier new tokens
+(csrc/kernels/attention_append.hip: MFMA attention with device-side lengths, split over the
+keys).  That is a second prompt over an existing cache, a chunked prefill, the scoring of a
+continuation, and the verification pass of greedy speculative decoding
+(:meth:`Generator.generate_speculative`, with :meth:`KVCache.truncate` as the rollback).
 """
 from __future__ import annotations
 
@@ -67,6 +74,28 @@ class KVCache:
         self.lens.zero_()
         self.pos = 0
         self.ragged = False
+
+    def truncate(self, lens, pos: Optional[int] = None) -> None:
+        """Roll the cache back to ``lens`` valid rows per sequence: a device tensor or host
+        ints [B], each at most the current value (not checked for a device tensor: that would
+        be a host synchronisation).  The cache becomes ragged.  ``pos`` is the new host upper
+        bound of the lengths; by default ``max(lens)`` for host ints and the old bound for a
+        device tensor.  Rows past ``lens[b]`` are stale, which every kernel tolerates."""
+        if isinstance(lens, torch.Tensor) and lens.device.type != "cpu":
+            if lens.numel() != self.B:
+                raise ValueError(f"truncate: {lens.numel()} lengths for a cache of {self.B} sequences")
+            self.lens.copy_(lens.reshape(-1))
+            bound = self.pos if pos is None else int(pos)
+        else:
+            host = torch.as_tensor(lens).reshape(-1).to(torch.int64)
+            if host.numel() != self.B or int(host.min()) < 0 or int(host.max()) > self.pos:
+                raise ValueError(f"truncate: needs {self.B} lengths in [0, {self.pos}]")
+            self.lens.copy_(host)
+            bound = int(host.max()) if pos is None else int(pos)
+        if bound < 0 or bound > self.max_len:
+            raise ValueError(f"truncate: pos {bound} outside [0, {self.max_len}]")
+        self.pos = bound
+        self.ragged = True
 
 
 class Generator:
@@ -267,6 +296,61 @@ class Generator:
         cache.pos = pos + 1
         return self._head(x, out=out)
 
+    @torch.no_grad()
+    def extend(self, tokens: torch.Tensor, cache: KVCache, counts=None, all_logits: bool = False) -> torch.Tensor:
+        """tokens [B, T]: append row b's first ``counts[b]`` tokens (host ints in [0, T];
+        None = all T) at positions ``cache.lens[b] ...`` and return the logits
+        [B, vocab_padded] of each row's last appended token, or [B, T, vocab_padded] of every
+        position with ``all_logits=True`` (rows ``t >= counts[b]``, and the single row of a
+        sequence with ``counts[b] == 0``, are unspecified but finite).
+
+        Works on an empty cache (a prefill), a uniform and a ragged one.  Every position is
+        read from ``cache.lens`` on the device; the host only checks ``cache.pos + T <=
+        cache.max_len`` and advances ``cache.pos`` by T.  A row with ``counts[b] == 0`` keeps
+        its cache rows and its length.  The cache becomes ragged unless it was uniform and
+        ``counts`` is None.  All B * T rows go through the norm / GEMM / activation ops and
+        :func:`ops.attn_append`; only the requested rows reach the LM head."""
+        cfg = self.cfg
+        if tokens.dim() != 2 or tokens.shape[0] != cache.B or tokens.shape[1] < 1:
+            raise ValueError(f"extend: tokens {tuple(tokens.shape)} do not fit a cache of {cache.B} sequences")
+        B, T = tokens.shape
+        if cache.pos + T > cache.max_len:
+            raise ValueError(f"extend: {cache.pos} cached + {T} new positions exceed the cache ({cache.max_len})")
+        dev = self.device
+        cnt = None
+        if counts is not None:
+            host = torch.as_tensor(counts).reshape(-1).to("cpu", torch.int64)
+            if host.numel() != B or int(host.min()) < 0 or int(host.max()) > T:
+                raise ValueError(f"extend: counts must hold {B} values in [0, {T}]")
+            cnt = host.to(dev, torch.int32)
+        H, KV, Dh = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
+        A = self.arena
+        base = cache.lens.clone()                    # the valid rows before this call
+        positions = (base[:, None] + torch.arange(T, device=dev, dtype=torch.int32)[None, :]).reshape(-1)
+        x = ops.embed_fwd(tokens.to(dev).reshape(-1), A.w("tok_embeddings.weight"),
+                          A.w("pos_embeddings.weight") if cfg.pos == "learned" else None, 1, positions=positions)
+        rope = cfg.pos == "rope"
+        for li, blk in enumerate(self.blocks):
+            h1 = self._norm(x, blk.w("attn_norm.weight"), blk.wb("attn_norm.bias"))
+            qkv, _ = ops.linear(h1, blk.w("attn.wqkv.weight"), blk.wb("attn.wqkv.bias"))
+            ops.rope_kv_append(qkv, blk.rope[0] if rope else None, blk.rope[1] if rope else None, cache.k[li],
+                               cache.v[li], base, None, H, KV, Dh, rope=rope, T=T, counts=cnt)
+            o = torch.empty(B * T, H * Dh, device=x.device, dtype=x.dtype)
+            ops.attn_append(qkv[:, : H * Dh], cache.k[li], cache.v[li], base, cnt, o, T, H, KV, Dh,
+                            max_len=cache.pos + T)
+            x2, _ = ops.linear(o, blk.w("attn.wo.weight"), blk.wb("attn.wo.bias"), residual=x)
+            x = self._ffn(blk, x2)
+        cache.lens.add_(T if cnt is None else cnt)
+        cache.pos += T
+        if cnt is not None:
+            cache.ragged = True
+        if all_logits:
+            return self._head(x).view(B, T, -1)
+        if cnt is None:
+            return self._head(x.view(B, T, -1)[:, -1].contiguous())
+        last = torch.arange(B, device=dev) * T + (cnt.long() - 1).clamp_(min=0)
+        return self._head(x.index_select(0, last))
+
     # ------------------------------------------------------------------ sampling loop
     def _pick(self, logits: torch.Tensor, temperature: float, top_k: Optional[int],
               gen: Optional[torch.Generator]) -> torch.Tensor:
@@ -412,3 +496,128 @@ class Generator:
             u_buf.copy_(u[N - 1])
             pick()
         return out, wpos
+
+    @torch.no_grad()
+    def generate_speculative(self, prompts, max_new_tokens: int, draft: "Generator", lookahead: int = 4,
+                             pad_token: int = 0):
+        """Greedy speculative decoding: ``(out, lengths, stats)`` with ``out`` / ``lengths`` as
+        in :meth:`generate_batch` and ``stats = {"rounds", "drafted", "accepted"}``.
+
+        ``draft`` is another :class:`Generator` over the same vocabulary.  Each round the
+        draft decodes up to ``lookahead`` tokens greedily over its own ragged cache, the target
+        runs one :meth:`extend` of those tokens behind its last one (``all_logits=True``),
+        and per row the longest prefix of drafted tokens equal to the target's argmax is
+        accepted, followed by the target's own next token; both caches are rolled back to the
+        accepted length (:meth:`KVCache.truncate`).  The tokens are the target's own greedy
+        continuation whatever the draft proposes; the draft only decides how many of them a
+        round yields (1 to ``lookahead + 1``).
+
+        Acceptance, the scatter into ``out`` and the new lengths are computed on the device.
+        The tokens each row gained are read back to the host once per round -- one
+        synchronisation per up to ``lookahead + 1`` tokens -- to bound ``cache.pos``, to give a
+        row that has its ``max_new_tokens`` a count of 0 and to end the loop.  The last rounds
+        draft fewer tokens, so that no row is asked for more than it may still emit.  Greedy
+        only: there is no sampling variant."""
+        cfg = self.cfg
+        V, N, K, dev = cfg.vocab_size, int(max_new_tokens), int(lookahead), self.device
+        if not isinstance(draft, Generator) or draft.cfg.vocab_size != V:
+            raise ValueError("generate_speculative: the draft must be a Generator over the same vocabulary")
+        if draft.device != dev:
+            raise ValueError("generate_speculative: the draft lives on another device")
+        rows = [torch.as_tensor(p).reshape(-1).to("cpu", torch.int64) for p in prompts]
+        if not rows or any(r.numel() < 1 for r in rows):
+            raise ValueError("generate_speculative: needs at least one prompt, each of at least one token")
+        if N < 0 or K < 1:
+            raise ValueError("generate_speculative: needs max_new_tokens >= 0 and lookahead >= 1")
+        lens = [int(r.numel()) for r in rows]
+        B, S0 = len(rows), max(lens)
+        limit = min(cfg.max_seq_len, draft.cfg.max_seq_len)
+        if S0 + N > limit:
+            raise ValueError(f"generate_speculative: {S0} prompt + {N} new tokens exceed max_seq_len = {limit} "
+                             "(the learned positions / RoPE table end there)")
+        if any(int(r.min()) < 0 or int(r.max()) >= V for r in rows):
+            raise ValueError(f"generate_speculative: prompt token outside the vocabulary [0, {V})")
+        pad = int(pad_token)
+        if not 0 <= pad < V:
+            raise ValueError(f"generate_speculative: pad_token {pad} outside the vocabulary [0, {V})")
+
+        tokens = torch.full((B, S0), pad, dtype=torch.int64)
+        for b, r in enumerate(rows):
+            tokens[b, : lens[b]] = r
+        tokens = tokens.to(dev)
+        W = S0 + N
+        # K + 1 spare columns: a round writes its K + 1 candidates unmasked behind the row's
+        # end; what lies beyond the final lengths is padded over at the end
+        buf = torch.full((B, W + K + 1), pad, device=dev, dtype=torch.int64)
+        buf[:, :S0] = tokens
+        wpos = torch.tensor(lens, device=dev, dtype=torch.int64)
+        stats = {"rounds": 0, "drafted": 0, "accepted": 0}
+        if N == 0:
+            return buf[:, :W].contiguous(), wpos, stats
+        cap = min(W + K + 1, limit)
+        tcache, dcache = self.new_cache(B, cap), draft.new_cache(B, cap)
+
+        def greedy(lg):
+            return lg[..., :V].float().argmax(-1)
+
+        cur = greedy(self.prefill(tokens, tcache, lens))       # the target's first token: in no cache yet
+        draft.prefill(tokens, dcache, lens)
+        buf.scatter_(1, wpos[:, None], cur[:, None])
+        wpos.add_(1)
+        made = [1] * B                                  # tokens emitted per row (host)
+        carry = [False] * B                             # the draft's cache lacks its own last token
+        carry_tok = torch.full((B,), pad, device=dev, dtype=torch.int64)
+        padcol = torch.full((B,), pad, device=dev, dtype=torch.int64)
+        while True:
+            rem = [N - m for m in made]
+            live = [r > 0 for r in rem]
+            if not any(live):
+                break
+            # host bounds of the lengths of the rows still running: every token but `cur`
+            bound = max(lens[b] + made[b] - 1 for b in range(B) if live[b])
+            tcache.pos = dcache.pos = bound
+            k = min(K, max(rem) - 1, tcache.max_len - bound - 1, dcache.max_len - bound - 1)
+            counts = [min(k + 1, r) for r in rem]
+            drafts = []
+            if k >= 1:
+                # the draft catches up with `cur` (and with its own last token where every
+                # draft of the last round was accepted), then decodes the rest one by one
+                two = any(c and l for c, l in zip(carry, live))
+                cflag = torch.tensor(carry, device=dev)
+                if two:
+                    tok = torch.stack([torch.where(cflag, carry_tok, cur), torch.where(cflag, cur, padcol)], 1)
+                    c2 = [(2 if carry[b] else 1) if live[b] else 0 for b in range(B)]
+                else:
+                    tok, c2 = cur[:, None], [1 if l else 0 for l in live]
+                d = greedy(draft.extend(tok, dcache, counts=c2))
+                drafts.append(d)
+                active = torch.tensor(live, device=dev).to(torch.uint8)
+                for _ in range(k - 1):
+                    d = greedy(draft.decode(d, dcache, active=active))
+                    drafts.append(d)
+            D = torch.stack(drafts, 1) if drafts else torch.empty(B, 0, device=dev, dtype=torch.int64)
+            cnt = torch.tensor(counts, device=dev, dtype=torch.int64)
+            base = tcache.lens.clone()
+            a = greedy(self.extend(torch.cat([cur[:, None], D], 1), tcache, counts=counts, all_logits=True))
+            # accepted drafts per row: the longest matching prefix, within the row's count
+            m = (D == a[:, :k]).long().cumprod(1).sum(1)
+            m = torch.minimum(m, (cnt - 1).clamp_(min=0))
+            gain = torch.where(cnt > 0, m + 1, torch.zeros_like(m))
+            buf.scatter_(1, wpos[:, None] + torch.arange(k + 1, device=dev)[None, :], a)
+            wpos.add_(gain)
+            cur = torch.where(cnt > 0, a.gather(1, m[:, None])[:, 0], cur)
+            new_lens = base + gain.to(torch.int32)
+            tcache.truncate(new_lens)
+            if k >= 1:
+                dcache.truncate(torch.minimum(dcache.lens, new_lens))
+                carry_tok = D[:, k - 1]
+            gained = gain.tolist()                      # the round's one host synchronisation
+            for b in range(B):
+                if live[b]:
+                    made[b] += gained[b]
+                    carry[b] = k >= 1 and gained[b] == k + 1
+                    stats["drafted"] += counts[b] - 1
+                    stats["accepted"] += gained[b] - 1
+            stats["rounds"] += 1
+        out = torch.where(torch.arange(W, device=dev)[None, :] < wpos[:, None], buf[:, :W], padcol[:, None])
+        return out, wpos, stats

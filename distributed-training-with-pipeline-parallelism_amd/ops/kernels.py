@@ -1070,19 +1070,81 @@ def attn_decode(q, k_cache, v_cache, lens, o, H: int, Hkv: int, D: int, scale: O
     return o
 
 
+def attn_append_plan(B: int, T: int, Hkv: int, rep: int, max_len: int) -> int:
+    """Key splits :func:`attn_append` picks (``splits=0``) for ``B`` sequences x ``T`` new
+    tokens x ``Hkv`` KV heads of ``rep`` query heads each over caches of up to ``max_len``
+    keys (csrc/kernels/attention_append.hip)."""
+    return int(_ext().attn_append_plan(int(B), int(T), int(Hkv), int(rep), int(max_len)))
+
+
+def attn_append(q, k_cache, v_cache, base, counts, o, T: int, H: int, Hkv: int, D: int,
+                scale: Optional[float] = None, splits: int = 0, max_len: Optional[int] = None):
+    """Attention of ``T`` new tokens per sequence over its KV cache.  q/o: [B*T, H*D] row
+    views (q is a slice of the packed qkv rows; row ``b*T + t`` is new token t of sequence
+    b); k_cache/v_cache: [B, Smax, Hkv*D] views that already hold the new tokens' rows at
+    ``base[b] + t``; base: int32 [B] on q's device, the valid cache rows before this call
+    (clamped to [0, Smax]); counts: int32 [B] on q's device or None (= T), how many of the
+    row's T tokens are real (clamped to [0, min(T, Smax - base)]).  Query (b, t) with
+    ``t < counts[b]`` sees the keys ``j <= base[b] + t``; a query with ``t >= counts[b]``
+    gets a zero row.  Cache rows at or beyond ``base[b] + counts[b]`` never enter a result.
+    ``max_len`` (a host int >= max(base + counts), default Smax) sizes the GPU grid;
+    ``splits``: 0 = the kernel's planner, n > 0 forces n key splits.  Writes o."""
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    if D not in (64, 128) and _gpu(q):
+        raise ValueError(f"attn_append: head_dim {D} is not supported by the HIP kernel (64 or 128)")
+    if H % Hkv or (_gpu(q) and H // Hkv > 8):
+        raise ValueError(f"attn_append: H = {H}, Hkv = {Hkv} is not supported (H % Hkv == 0, H / Hkv <= 8)")
+    B, Smax, T = k_cache.shape[0], k_cache.shape[1], int(T)
+    if T < 1 or q.shape[0] != B * T or o.shape[0] != B * T:
+        raise ValueError(f"attn_append: q/o must hold B * T = {B} * {T} rows")
+    if base.dtype != torch.int32 or base.device != q.device or base.numel() != B:
+        raise ValueError("attn_append: base must be an int32 [B] tensor on q's device")
+    if counts is not None and (counts.dtype != torch.int32 or counts.device != q.device or counts.numel() != B):
+        raise ValueError("attn_append: counts must be an int32 [B] tensor on q's device")
+    max_len = Smax if max_len is None else int(max_len)
+    if _gpu(q):
+        _ext().attn_append(q, k_cache, v_cache, base, counts, o, T, int(H), int(Hkv), int(D), max_len, float(scale),
+                           int(splits))
+        return o
+    rep = H // Hkv
+    cl = [T] * B if counts is None else counts.tolist()
+    for b, n0 in enumerate(base.tolist()):
+        n0 = max(0, min(int(n0), Smax))
+        c = max(0, min(int(cl[b]), T, Smax - n0))
+        o[b * T + c:(b + 1) * T, : H * D].zero_()
+        if c == 0:
+            continue
+        n = n0 + c
+        Q = q[b * T:b * T + c, : H * D].float().reshape(c, H, D).permute(1, 0, 2)
+        K = k_cache[b, :n, : Hkv * D].float().reshape(n, Hkv, D).permute(1, 0, 2).repeat_interleave(rep, 0)
+        V = v_cache[b, :n, : Hkv * D].float().reshape(n, Hkv, D).permute(1, 0, 2).repeat_interleave(rep, 0)
+        s = (Q @ K.transpose(-1, -2)) * scale
+        hidden = torch.arange(n)[None, :] > (n0 + torch.arange(c))[:, None]
+        p = torch.softmax(s.masked_fill(hidden, float("-inf")), -1)
+        o[b * T:b * T + c, : H * D].copy_((p @ V).permute(1, 0, 2).reshape(c, H * D).to(o.dtype))
+    return o
+
+
 # ======================================================================================
 # the ragged decode step: K/V append at a device-side position, on-device sampling
 # ======================================================================================
 def rope_kv_append(qkv: torch.Tensor, cos: Optional[torch.Tensor], sin: Optional[torch.Tensor], k_cache: torch.Tensor,
                    v_cache: torch.Tensor, pos: torch.Tensor, active: Optional[torch.Tensor], H: int, Hkv: int, Dh: int,
-                   rope: bool = True):
-    """One new token per sequence.  qkv: packed [B, (H + 2 Hkv) * Dh] rows; pos: int32 [B] on
-    qkv's device, clamped to [0, Smax - 1]; active: uint8 [B] or None (all active).  For an
-    active row b: q is rotated in place at position pos[b] (``rope``), k is rotated and
-    written to ``k_cache[b, pos[b]]`` (the k columns of qkv keep their unrotated values), v is
-    copied to ``v_cache[b, pos[b]]``.  The rotation is :func:`rope_`'s at ``pos_offset =
-    pos[b]``, bit for bit.  An inactive row is left alone: nothing is written for it."""
-    B, Smax = qkv.shape[0], k_cache.shape[1]
+                   rope: bool = True, T: int = 1, counts: Optional[torch.Tensor] = None):
+    """``T`` new tokens per sequence (default one).  qkv: packed [B*T, (H + 2 Hkv) * Dh] rows,
+    row ``b*T + t`` being token t of sequence b at position ``p = pos[b] + t``; pos: int32 [B]
+    on qkv's device (positions are clamped to [0, Smax - 1]); active: uint8 [B] or None (all
+    active); counts: int32 [B] or None (all T): only rows ``t < counts[b]`` are touched.  For
+    such a row of an active sequence: q is rotated in place at position p (``rope``), k is
+    rotated and written to ``k_cache[b, p]`` (the k columns of qkv keep their unrotated
+    values), v is copied to ``v_cache[b, p]``.  The rotation is :func:`rope_`'s at
+    ``pos_offset = p``, bit for bit.  Any other row is left alone: nothing is written for it."""
+    T = int(T)
+    if T < 1 or qkv.shape[0] % T:
+        raise ValueError(f"rope_kv_append: {qkv.shape[0]} qkv rows are no multiple of T = {T}")
+    B, Smax = qkv.shape[0] // T, k_cache.shape[1]
+    if counts is not None and (counts.dtype != torch.int32 or counts.device != qkv.device or counts.numel() != B):
+        raise ValueError("rope_kv_append: counts must be int32 [B] on qkv's device")
     if pos.dtype != torch.int32 or pos.device != qkv.device or pos.numel() != B:
         raise ValueError("rope_kv_append: pos must be int32 [B] on qkv's device")
     if active is not None and (active.dtype != torch.uint8 or active.device != qkv.device or active.numel() != B):
@@ -1093,11 +1155,18 @@ def rope_kv_append(qkv: torch.Tensor, cos: Optional[torch.Tensor], sin: Optional
         if Dh not in (64, 128):
             raise ValueError(f"rope_kv_append: head_dim {Dh} is not supported by the HIP kernel (64 or 128)")
         _ext().rope_kv_append(qkv, cos if rope else None, sin if rope else None, k_cache, v_cache, pos, active,
-                              int(H), int(Hkv), int(Dh), bool(rope))
+                              int(H), int(Hkv), int(Dh), bool(rope), T, counts)
         return qkv
     half = Dh // 2
-    p = pos.long().clamp(0, Smax - 1)
-    rows = torch.arange(B) if active is None else torch.nonzero(active.reshape(-1) != 0)[:, 0]
+    tt = torch.arange(T).repeat(B)                                   # token index of every row
+    bb = torch.arange(B).repeat_interleave(T)                        # ... and its sequence
+    p = (pos.long().clamp(0, Smax - 1)[bb] + tt).clamp(max=Smax - 1)
+    on = torch.ones(B * T, dtype=torch.bool)
+    if active is not None:
+        on &= active.reshape(-1)[bb] != 0
+    if counts is not None:
+        on &= tt < counts.long()[bb]
+    rows = torch.nonzero(on)[:, 0]
     if rows.numel() == 0:
         return qkv
     x = qkv[rows].float().reshape(-1, H + 2 * Hkv, Dh)
@@ -1109,8 +1178,8 @@ def rope_kv_append(qkv: torch.Tensor, cos: Optional[torch.Tensor], sin: Optional
         rot = x[:, : H + Hkv]
     if rope:
         qkv[rows, : H * Dh] = rot[:, :H].reshape(-1, H * Dh).to(qkv.dtype)
-    k_cache[rows, p[rows], : Hkv * Dh] = rot[:, H:].reshape(-1, Hkv * Dh).to(k_cache.dtype)
-    v_cache[rows, p[rows], : Hkv * Dh] = x[:, H + Hkv:].reshape(-1, Hkv * Dh).to(v_cache.dtype)
+    k_cache[bb[rows], p[rows], : Hkv * Dh] = rot[:, H:].reshape(-1, Hkv * Dh).to(k_cache.dtype)
+    v_cache[bb[rows], p[rows], : Hkv * Dh] = x[:, H + Hkv:].reshape(-1, Hkv * Dh).to(v_cache.dtype)
     return qkv
 
 

@@ -5,6 +5,8 @@
         --temperature 0.8 --top-k 40 --seed 1 --device cuda
     python generate.py --checkpoint DIR --prompt "1,2,3;7,8" --max-new-tokens 16 \
         --temperature 0.8 --top-k 40 --top-p 0.9 --stop-token 0
+    python generate.py --checkpoint DIR --draft-checkpoint SMALL_DIR --lookahead 4 \
+        --prompt "1,2,3;7,8" --max-new-tokens 16
 
 The model configuration comes from the checkpoint's manifest; the weights are found by FQN,
 so a checkpoint written at any PP / DP degree loads into this single process.  Prompts are
@@ -16,6 +18,11 @@ go through ``Generator.generate``.  Prompts of different lengths, or any of thos
 through ``Generator.generate_batch`` (positions and sampling on the device): each printed
 row then ends with its last valid token -- the stop token if it was produced -- and the
 padding is not printed.
+
+``--draft-checkpoint`` routes to ``Generator.generate_speculative`` (greedy only): a smaller
+model over the same vocabulary drafts ``--lookahead`` tokens per round and the checkpoint's
+model verifies them in one pass.  The printed rows are the model's own greedy continuation;
+the acceptance rate goes to stderr.
 """
 from __future__ import annotations
 
@@ -42,6 +49,9 @@ def main(argv=None) -> int:
     ap.add_argument("--stop-token", type=int, default=None, help="a sequence ends once it produces this id")
     ap.add_argument("--pad-token", type=int, default=None, help="id that fills finished rows (default 0; not printed)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--draft-checkpoint", default=None, help="speculative decoding: checkpoint directory of the "
+                    "draft model (same vocabulary; greedy only)")
+    ap.add_argument("--lookahead", type=int, default=4, help="tokens the draft proposes per round")
     ap.add_argument("--device", choices=("cpu", "cuda"), default=None, help="default: cuda when available")
     a = ap.parse_args(argv)
 
@@ -53,6 +63,20 @@ def main(argv=None) -> int:
     bad = [t for r in rows for t in r if not 0 <= t < gen.cfg.vocab_size]
     if bad:
         raise ValueError(f"--prompt: token id {bad[0]} outside the vocabulary [0, {gen.cfg.vocab_size})")
+    if a.draft_checkpoint is not None:
+        if a.temperature != 0 or a.top_k is not None or a.top_p is not None or a.stop_token is not None:
+            raise ValueError("--draft-checkpoint: speculative decoding is greedy only (no --temperature / --top-k / "
+                             "--top-p / --stop-token)")
+        draft = mipipe.Generator.load(a.draft_checkpoint, device=gen.device, dtype=gen.dtype)
+        out, lengths, stats = gen.generate_speculative([torch.tensor(r, dtype=torch.int64) for r in rows],
+                                                       a.max_new_tokens, draft, lookahead=a.lookahead,
+                                                       pad_token=a.pad_token or 0)
+        for r, n in zip(out.tolist(), lengths.tolist()):
+            print(",".join(str(t) for t in r[:n]))
+        rate = stats["accepted"] / stats["drafted"] if stats["drafted"] else 0.0
+        print(f"speculative: {stats['rounds']} rounds, {stats['accepted']} of {stats['drafted']} drafted tokens "
+              f"accepted ({rate:.1%})", file=sys.stderr)
+        return 0
     ragged = len({len(r) for r in rows}) != 1
     if ragged or a.top_p is not None or a.stop_token is not None or a.pad_token is not None:
         out, lengths = gen.generate_batch([torch.tensor(r, dtype=torch.int64) for r in rows], a.max_new_tokens,

@@ -35,7 +35,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # per-file compile flags.  attention.hip: no SLP packing -- -O3 pairs the softmax's independent
 # f32 adds / multiplies into v_pk_*_f32, which beside MFMAs cost more issue cycles than the
 # scalar ops they replace (MI355X_MICROARCH.md, 'price of one filler beside MFMAs')
-FILE_FLAGS = {"attention.hip": ["-fno-slp-vectorize"], "attention_doc.hip": ["-fno-slp-vectorize"]}
+FILE_FLAGS = {"attention.hip": ["-fno-slp-vectorize"], "attention_doc.hip": ["-fno-slp-vectorize"],
+              "attention_append.hip": ["-fno-slp-vectorize"]}
 
 
 def _torch_paths():
