@@ -13,6 +13,7 @@
 #include <string>
 
 #include "mp_gemm_plan.h"
+#include "mp_gemv_plan.h"
 
 extern "C" {
 int mp_norm_fwd(int f32, int rms, const void* a, const void* b, const void* w, const void* bias, void* s_out, void* y,
@@ -120,6 +121,10 @@ int mp_probe_clock_khz();
 int mp_gemm(const void* A, const void* B, void* C, const void* bias, const void* residual, void* aux, int M, int N,
             int K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ld_res, int64_t ld_aux, int transA, int transB,
             int epilogue, int c_f32_accum, float alpha, hipStream_t st);
+int mp_gemv_skinny(const void* w, const float* scale, int wbytes, const void* x, void* y, const void* bias,
+                   const void* res, int M, int N, int K, int64_t ldx, int64_t ldy, int64_t ldr, int gelu,
+                   int force_split, hipStream_t st);
+int mp_dequant_w8(const void* q, const float* scale, void* out, int64_t N, int64_t K, hipStream_t st);
 }
 
 namespace {
@@ -869,6 +874,63 @@ void gemm(torch::Tensor A, torch::Tensor B, torch::Tensor C, c10::optional<torch
 // What the v2 GEMM will run (mp_gemm_plan.h).  env: the planner switches by name over their
 // defaults; none: the process environment, read once.
 using PlanEnvDict = std::map<std::string, std::string>;
+// y[M, N] = epi(x[M, K] @ What^T), M <= 16 (csrc/kernels/gemv_skinny.hip): w int8 [N, K] with scale f32 [N],
+// or w bf16 [N, K] without.  No allocation, no synchronisation.
+void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> scale, torch::Tensor y,
+                 c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, bool gelu,
+                 int64_t force_split) {
+  // x / y / residual: bf16 rows of any stride
+  auto rows = [](const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16 && t.dim() == 2 && t.stride(1) == 1 &&
+                    (t.size(0) == 1 || t.stride(0) >= t.size(1)),
+                name, " must be bf16 GPU rows [M, cols] with a unit inner stride");
+  };
+  rows(x, "gemv_skinny: x");
+  rows(y, "gemv_skinny: y");
+  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous(), "gemv_skinny: w must be a contiguous [N, K] GPU matrix");
+  const bool w8 = w.scalar_type() == torch::kInt8;
+  TORCH_CHECK(w8 || w.scalar_type() == torch::kBFloat16, "gemv_skinny: w must be int8 or bf16, got ", w.scalar_type());
+  TORCH_CHECK(w8 == scale.has_value(), "gemv_skinny: int8 weights take a scale, bf16 weights none");
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  TORCH_CHECK(M >= 1 && M <= gemv::MAX_M, "gemv_skinny: M = ", M, " outside [1, ", gemv::MAX_M, "]");
+  TORCH_CHECK(w.size(1) == K && y.size(0) == M && y.size(1) == N, "gemv_skinny: shapes x ", x.sizes(), " w ", w.sizes(), " y ", y.sizes());
+  TORCH_CHECK(gemv::plan(N, K, w8 ? 1 : 2, (int)force_split).rows != 0, "gemv_skinny: N = ", N, ", K = ", K,
+              ", force_split = ", force_split, " is not supported (K a multiple of 32, force_split <= 16)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0, "gemv_skinny: w must be 16-byte aligned");
+  if (w8) {
+    req(*scale, torch::kFloat32, "gemv_skinny: scale");
+    TORCH_CHECK(scale->numel() == N && scale->is_contiguous(), "gemv_skinny: scale must hold N contiguous values");
+  }
+  if (bias.has_value()) {
+    req(*bias, torch::kBFloat16, "gemv_skinny: bias");
+    TORCH_CHECK(bias->numel() == N && bias->is_contiguous(), "gemv_skinny: bias must hold N contiguous values");
+  }
+  TORCH_CHECK(!gelu || bias.has_value(), "gemv_skinny: the GELU epilogue needs a bias");
+  TORCH_CHECK(!gelu || !residual.has_value(), "gemv_skinny: no residual behind GELU");
+  int64_t ldr = 0;
+  if (residual.has_value()) {
+    rows(*residual, "gemv_skinny: residual");
+    TORCH_CHECK(residual->size(0) == M && residual->size(1) == N, "gemv_skinny: residual must be [M, N]");
+    ldr = residual->stride(0);
+  }
+  check(mp_gemv_skinny(w.data_ptr(), w8 ? scale->data_ptr<float>() : nullptr, w8 ? 1 : 2, x.data_ptr(), y.data_ptr(),
+                       ptr_or_null(bias), ptr_or_null(residual), (int)M, (int)N, (int)K, x.stride(0), y.stride(0), ldr,
+                       gelu ? 1 : 0, (int)force_split, cur_stream()),
+        "gemv_skinny");
+}
+
+void dequant_w8(torch::Tensor q, torch::Tensor scale, torch::Tensor out) {
+  req(q, torch::kInt8, "dequant_w8: q");
+  req(scale, torch::kFloat32, "dequant_w8: scale");
+  req(out, torch::kBFloat16, "dequant_w8: out");
+  TORCH_CHECK(q.dim() == 2 && q.is_contiguous() && out.is_contiguous() && out.numel() == q.numel() &&
+                  scale.is_contiguous() && scale.numel() == q.size(0),
+              "dequant_w8: q [N, K], scale [N], out [N, K], all contiguous");
+  TORCH_CHECK(q.size(1) % 16 == 0, "dequant_w8: K = ", q.size(1), " must be a multiple of 16");
+  check(mp_dequant_w8(q.data_ptr(), scale.data_ptr<float>(), out.data_ptr(), q.size(0), q.size(1), cur_stream()),
+        "dequant_w8");
+}
+
 g2::Plan gemm2_plan(int64_t M, int64_t N, int64_t K, bool transA, bool transB, bool accum, int64_t force_cfg,
                     const std::optional<PlanEnvDict>& env) {
   g2::PlanEnv parsed;
@@ -1264,5 +1326,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     const int big = mp_gemm_f32_plan((int)M, (int)N, (int)K, (int)force_ks, &split, &sk_grid, &sk_chunk);
     return std::make_tuple(big != 0, split, sk_grid, sk_chunk);
   }, "what gemm_f32_ex will run: (128x128 engine, split-K factor, stream-K workgroups, K-tile pairs per workgroup)");
+  m.def("gemv_skinny", &gemv_skinny, pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("scale"), pybind11::arg("y"),
+        pybind11::arg("bias"), pybind11::arg("residual"), pybind11::arg("gelu") = false, pybind11::arg("force_split") = 0);
+  m.def("dequant_w8", &dequant_w8);
+  m.def("gemv_plan", [](int64_t N, int64_t K, int64_t wbytes, int64_t force_split) {
+    const gemv::Plan p = gemv::plan(N, K, (int)wbytes, (int)force_split);
+    TORCH_CHECK(p.rows != 0, "gemv_plan: N = ", N, ", K = ", K, ", wbytes = ", wbytes, ", force_split = ", force_split,
+                " is not supported");
+    return std::make_tuple(p.rows, p.ksplit);
+  }, pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("wbytes"), pybind11::arg("force_split") = 0,
+     "(weight rows per workgroup, K-splits = waves per workgroup) of the skinny-M kernel");
   m.def("gemm2_has_probe_engines", []() { return mp_gemm2_has_probe_engines() != 0; });
 }

@@ -27,17 +27,23 @@ at ``cache.lens[b] ...`` and attend causally over the cache plus the earlier new
 keys).  That is a second prompt over an existing cache, a chunked prefill, the scoring of a
 continuation, and the verification pass of greedy speculative decoding
 (:meth:`Generator.generate_speculative`, with :meth:`KVCache.truncate` as the rollback).
+
+int8 weight-only inference (``Generator(..., weights="int8")``, :class:`QuantWeights`): the
+block matrices and the LM head are held as int8 with one f32 scale per output row and no
+training state, and linear layers of at most 16 rows stream them through
+csrc/kernels/gemv_skinny.hip (:func:`ops.linear_w8`); ``skinny=True`` runs bf16 weights
+through the same kernel.  Every mode above works on either kind of generator.
 """
 from __future__ import annotations
 
 import dataclasses
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 import torch
 
 from .. import ops
 from .config import NativeConfig
-from .native import Block, NativeModel
+from .native import Block, NativeModel, ParamSpec, _name_seed, block_param_specs
 
 
 def _check_generative(cfg: NativeConfig) -> None:
@@ -98,14 +104,164 @@ class KVCache:
         self.ragged = True
 
 
+QUANTIZED = ("attn.wqkv.weight", "attn.wo.weight", "ffn.w1.weight", "ffn.w2.weight", "ffn.w13.weight")
+
+
+def model_param_specs(cfg: NativeConfig) -> List[ParamSpec]:
+    """The parameters of a whole single-stage generative model, by the FQNs a
+    :class:`NativeModel` at ``pp = 1`` (and a checkpoint) gives them."""
+    d = cfg.d_model
+    specs = [ParamSpec("tok_embeddings.weight", (cfg.vocab_padded, d), "normal", False, cfg.init_std)]
+    if cfg.pos == "learned":
+        specs.append(ParamSpec("pos_embeddings.weight", (cfg.max_seq_len, d), "normal", False, 0.01))
+    for i in range(cfg.n_layers):
+        specs += block_param_specs(cfg, i)
+    if cfg.final_norm:
+        specs.append(ParamSpec("norm.weight", (d,), "ones", False))
+        if cfg.norm == "layernorm":
+            specs.append(ParamSpec("norm.bias", (d,), "zeros", False))
+    if not cfg.tie_embeddings:
+        specs.append(ParamSpec("output.weight", (cfg.vocab_padded, d), "normal", True, cfg.init_std))
+    return specs
+
+
+class QuantWeights:
+    """Inference-only weights of a whole model with its matrices in int8: what a quantised
+    :class:`Generator` holds instead of a :class:`ParamArena`.
+
+    Every block matrix (``QUANTIZED``) and the LM head are kept as ``q[name]`` (int8 [N, K])
+    and ``scale[name]`` (f32 [N]), the format of :func:`ops.quantize_w8`; embeddings, norms and
+    biases as ``dtype`` tensors.  With tied embeddings the head is an int8 copy of the token
+    table (``q["tok_embeddings.weight"]``) beside the table itself.  There is no f32 master, no
+    gradient, no transposed copy and no dense copy of a quantised matrix.  ``w`` / ``has``
+    answer as the arena does for the dense tensors."""
+
+    def __init__(self, cfg: NativeConfig, device, dtype=torch.bfloat16):
+        self.cfg = cfg
+        self.device = torch.device(device)
+        self.dtype = dtype
+        specs = model_param_specs(cfg)
+        self.specs = {s.name: s for s in specs}
+        self.order = [s.name for s in specs]
+        self.head_name = "tok_embeddings.weight" if cfg.tie_embeddings else "output.weight"
+        self.q: Dict[str, torch.Tensor] = {}
+        self.scale: Dict[str, torch.Tensor] = {}
+        self.dense: Dict[str, torch.Tensor] = {}
+
+    def quantized(self, name: str) -> bool:
+        return name == self.head_name or name.endswith(QUANTIZED)
+
+    def has(self, name: str) -> bool:
+        return name in self.specs
+
+    def w(self, name: str) -> torch.Tensor:
+        return self.dense[name]
+
+    def put(self, name: str, t: torch.Tensor) -> None:
+        """Store one parameter from its full-precision values: quantised on the target
+        device where the name calls for it, cast to ``dtype`` otherwise."""
+        # quantised where the values are (a checkpoint's tensors on the host: the device then
+        # sees only the int8 matrix, never an f32 temporary whose freed block a later tensor
+        # would take over whole); quantize_w8 gives the same values on either device
+        s = self.specs[name]
+        t = t.detach().float().reshape(s.shape)
+        if self.quantized(name):
+            q, scale = ops.quantize_w8(t)
+            self.q[name], self.scale[name] = q.to(self.device), scale.to(self.device)
+        # dense: everything but the block matrices and an untied head (a tied head is also
+        # the embedding table, which stays dense)
+        if not name.endswith(QUANTIZED) and (name != self.head_name or self.cfg.tie_embeddings):
+            self.dense[name] = t.to(self.dtype, copy=True).contiguous().to(self.device)     # never a view of the source
+
+    def init_params(self, seed: int = 0) -> None:
+        """The values :meth:`ParamArena.init_params` draws for the same seed, quantised."""
+        gdev = "cuda" if self.device.type == "cuda" else "cpu"
+        for name in self.order:
+            s = self.specs[name]
+            if s.init == "zeros":
+                v = torch.zeros(s.shape)
+            elif s.init == "ones":
+                v = torch.ones(s.shape)
+            else:
+                g = torch.Generator(device=gdev).manual_seed(_name_seed(seed, name))
+                v = torch.randn(s.shape, generator=g, device=gdev, dtype=torch.float32) * s.std
+            self.put(name, v)
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        missing = [n for n in self.order if n not in sd]
+        if missing:
+            raise KeyError(f"missing keys: {missing[:5]}...")
+        for n in self.order:
+            self.put(n, sd[n])
+
+    def effective_state_dict(self) -> Dict[str, torch.Tensor]:
+        """f32 CPU tensors by FQN of the weights this generator computes with: ``q * scale``
+        for the quantised matrices (also for the head of an untied model), the stored values
+        otherwise.  With tied embeddings ``tok_embeddings.weight`` is the embedding table and
+        the head's effective weight is under ``"lm_head"``."""
+        out = {}
+        for n in self.order:
+            if n in self.dense:
+                out[n] = self.dense[n].detach().float().cpu()
+            else:
+                out[n] = (self.q[n].float() * self.scale[n][:, None]).cpu()
+        if self.cfg.tie_embeddings:
+            n = self.head_name
+            out["lm_head"] = (self.q[n].float() * self.scale[n][:, None]).cpu()
+        return out
+
+    def max_matrix_numel(self) -> int:
+        return max(q.numel() for q in self.q.values())
+
+
+class _QBlock:
+    """What the generator reads of a :class:`Block`, over :class:`QuantWeights`."""
+
+    def __init__(self, idx: int, weights: QuantWeights, rope=None):
+        self.i = idx
+        self.A = weights
+        self.P = f"layers.{idx}."
+        self.rope = rope
+
+    def w(self, n):
+        return self.A.w(self.P + n)
+
+    def wb(self, n):
+        return self.A.w(self.P + n) if self.A.has(self.P + n) else None
+
+
+def _check_weights(weights: str, skinny: bool) -> None:
+    if weights not in ("bf16", "int8"):
+        raise ValueError(f"Generator: weights must be 'bf16' or 'int8', got {weights!r}")
+    if skinny and weights != "bf16":
+        raise ValueError("Generator: skinny=True is the bf16 weights' opt-in (int8 weights always use the skinny kernel)")
+
+
 class Generator:
     """KV-cache inference over one whole-model :class:`NativeModel` (``recompute=False``,
-    dropout off: the training forward hands ``cfg.dropout`` to its kernels)."""
+    dropout off: the training forward hands ``cfg.dropout`` to its kernels).
 
-    def __init__(self, cfg: NativeConfig, device, dtype=torch.bfloat16, seed: int = 0, init: bool = True):
+    ``weights="int8"``: the block matrices and the LM head are quantised per output row
+    (:func:`ops.quantize_w8`) and the generator holds :class:`QuantWeights` instead of a model
+    and its arena (``self.model`` is None).  Linear layers of at most ``ops.W8_SKINNY_MAX_M``
+    rows read the int8 matrix directly (:func:`ops.linear_skinny`); larger ones (a prefill)
+    dequantise into one scratch matrix, allocated on the first call that needs it.  GELU /
+    SwiGLU models only.  ``skinny=True`` (bf16 weights on the GPU only): linear layers of at
+    most 16 rows run the bf16 instantiation of the same kernel instead of the training GEMM."""
+
+    def __init__(self, cfg: NativeConfig, device, dtype=torch.bfloat16, seed: int = 0, init: bool = True,
+                 weights: str = "bf16", skinny: bool = False):
         _check_generative(cfg)
+        _check_weights(weights, skinny)
         cfg = dataclasses.replace(cfg, dropout=0.0)
+        if weights == "int8":
+            qw = QuantWeights(cfg, device, dtype)
+            if init:
+                qw.init_params(seed)
+            self._bind_quant(qw)
+            return
         self._bind(NativeModel(cfg, 0, 1, torch.device(device), seed=seed, recompute=False, dtype=dtype, init=init))
+        self.skinny = bool(skinny)
 
     def _bind(self, model: NativeModel) -> None:
         self.model = model
@@ -114,26 +270,56 @@ class Generator:
         self.device = model.device
         self.dtype = model.arena.dtype
         self.blocks: List[Block] = model.blocks
+        self.weights = "bf16"
+        self.skinny = False
+        self._scratch = None
+
+    def _bind_quant(self, qw: QuantWeights) -> None:
+        cfg = qw.cfg
+        self.model = None
+        self.cfg = cfg
+        self.arena = qw
+        self.device = qw.device
+        self.dtype = qw.dtype
+        rope = None
+        if cfg.pos == "rope":
+            rope = ops.rope_tables(cfg.max_seq_len, cfg.head_dim, cfg.rope_theta, self.device)
+        self.blocks = [_QBlock(i, qw, rope) for i in range(cfg.n_layers)]
+        self.weights = "int8"
+        self.skinny = False
+        self._scratch: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------ constructors
     @classmethod
-    def from_model(cls, model: NativeModel) -> "Generator":
+    def from_model(cls, model: NativeModel, weights: str = "bf16", skinny: bool = False) -> "Generator":
         """Wrap an existing single-stage model (``trainer.stages[0].model`` at ``pp = 1``).
-        The weights are the model's arena itself: nothing is copied, and a later optimizer
-        step is seen by the generator."""
+        With bf16 weights they are the model's arena itself: nothing is copied, and a later
+        optimizer step is seen by the generator.  ``weights="int8"`` takes a quantised
+        snapshot of the master weights instead: the model is left untouched, and the
+        generator does NOT see later optimizer steps (build a new one after training on)."""
         _check_generative(model.cfg)
+        _check_weights(weights, skinny)
         if model.num_stages != 1 or model.split_head:
             raise ValueError("Generator.from_model needs a single-stage model that owns its LM head (pp = 1)")
         self = cls.__new__(cls)
+        if weights == "int8":
+            qw = QuantWeights(dataclasses.replace(model.cfg, dropout=0.0), model.device, model.arena.dtype)
+            with model.arena.unsharded():
+                for n in qw.order:
+                    qw.put(n, model.arena.master_view(n))
+            self._bind_quant(qw)
+            return self
         self._bind(model)
+        self.skinny = bool(skinny)
         return self
 
     @classmethod
-    def load(cls, path: str, device=None, dtype=None) -> "Generator":
+    def load(cls, path: str, device=None, dtype=None, weights: str = "bf16", skinny: bool = False) -> "Generator":
         """Weights-only load of a checkpoint directory written by ``save_checkpoint`` at any
         PP / DP degree or head mode (the tensors are found by FQN).  Defaults: the GPU in
-        bf16 when there is one, else the CPU in f32."""
-        from ..utils.checkpoint import load_weights, read_manifest
+        bf16 when there is one, else the CPU in f32.  ``weights="int8"`` quantises tensor by
+        tensor while loading (deterministic: the same checkpoint gives the same int8 values)."""
+        from ..utils.checkpoint import iter_weights, load_weights, read_manifest
         man = read_manifest(path)
         cfg = NativeConfig(**man["model"])
         if device is None:
@@ -141,9 +327,36 @@ class Generator:
         device = torch.device(device)
         if dtype is None:
             dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
-        self = cls(cfg, device, dtype=dtype, init=False)
+        self = cls(cfg, device, dtype=dtype, init=False, weights=weights, skinny=skinny)
+        if weights == "int8":
+            for name, t in iter_weights(path, self.arena.order):
+                self.arena.put(name, t)
+            return self
         load_weights([self.arena], path, strict=True)
         return self
+
+    # ------------------------------------------------------------------ linear layers
+    def _linear(self, x: torch.Tensor, wname: str, bname: Optional[str] = None, act: str = "none",
+                residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        A = self.arena
+        bias = A.w(bname) if bname is not None and A.has(bname) else None
+        if self.weights == "int8":
+            key = A.head_name if wname == "lm_head" else wname
+            q, scale = A.q[key], A.scale[key]
+            scratch = None
+            if x.is_cuda and (x.shape[0] > ops.W8_SKINNY_MAX_M or q.shape[1] % 32 != 0):
+                if self._scratch is None:
+                    if torch.cuda.is_current_stream_capturing():
+                        raise RuntimeError("Generator: the dequantisation scratch cannot be allocated inside a graph "
+                                           "capture (run one step eagerly first)")
+                    self._scratch = torch.empty(A.max_matrix_numel(), device=self.device, dtype=torch.bfloat16)
+                scratch = self._scratch
+            return ops.linear_w8(x, q, scale, bias, act, residual, out, scratch=scratch)
+        w = self.model.head_weight() if wname == "lm_head" else A.w(wname)
+        if self.skinny and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[0] <= ops.SKINNY_MAX_M \
+                and w.shape[1] % 32 == 0 and act in ("none", "gelu", "gelu_tanh"):
+            return ops.linear_skinny(x, w, None, bias, act, residual, out)
+        return ops.linear(x, w, bias, act=act, residual=residual, out=out)[0]
 
     # ------------------------------------------------------------------ cache
     def new_cache(self, B: int, max_len: Optional[int] = None) -> KVCache:
@@ -157,17 +370,15 @@ class Generator:
         cfg = self.cfg
         h2 = self._norm(x2, blk.w("ffn_norm.weight"), blk.wb("ffn_norm.bias"))
         if cfg.activation == "swiglu":
-            gu, _ = ops.linear(h2, blk.w("ffn.w13.weight"))
-            y, _ = ops.linear(ops.swiglu_fwd(gu), blk.w("ffn.w2.weight"), residual=x2)
-        else:
-            g, _ = ops.linear(h2, blk.w("ffn.w1.weight"), blk.wb("ffn.w1.bias"), act=cfg.activation)
-            y, _ = ops.linear(g, blk.w("ffn.w2.weight"), blk.wb("ffn.w2.bias"), residual=x2)
-        return y
+            gu = self._linear(h2, blk.P + "ffn.w13.weight")
+            return self._linear(ops.swiglu_fwd(gu), blk.P + "ffn.w2.weight", residual=x2)
+        g = self._linear(h2, blk.P + "ffn.w1.weight", blk.P + "ffn.w1.bias", act=cfg.activation)
+        return self._linear(g, blk.P + "ffn.w2.weight", blk.P + "ffn.w2.bias", residual=x2)
 
     def _qkv(self, blk: Block, x: torch.Tensor, S: int, pos: int) -> torch.Tensor:
         cfg = self.cfg
         h1 = self._norm(x, blk.w("attn_norm.weight"), blk.wb("attn_norm.bias"))
-        qkv, _ = ops.linear(h1, blk.w("attn.wqkv.weight"), blk.wb("attn.wqkv.bias"))
+        qkv = self._linear(h1, blk.P + "attn.wqkv.weight", blk.P + "attn.wqkv.bias")
         if cfg.pos == "rope":
             ops.rope_(qkv, blk.rope[0], blk.rope[1], S, cfg.n_heads, cfg.n_kv_heads, cfg.head_dim, pos_offset=pos)
         return qkv
@@ -177,9 +388,7 @@ class Generator:
         A = self.arena
         if self.cfg.final_norm:
             h = self._norm(h, A.w("norm.weight"), A.w("norm.bias") if A.has("norm.bias") else None)
-        logits, _ = ops.linear(h, self.model.head_weight(), A.w("output.bias") if A.has("output.bias") else None,
-                               out=out)
-        return logits
+        return self._linear(h, "lm_head", "output.bias", out=out)
 
     def _embed(self, tokens: torch.Tensor, S: int, pos: int) -> torch.Tensor:
         A = self.arena
@@ -216,7 +425,7 @@ class Generator:
             o = torch.empty(B * S, H * Dh, device=x.device, dtype=x.dtype)
             lse = torch.empty(B * H * S, device=x.device, dtype=torch.float32)
             ops.attn_fwd(q, k, v, o, lse, B, S, S, H, KV, Dh, True, p_drop=0.0)
-            x2, _ = ops.linear(o, blk.w("attn.wo.weight"), blk.wb("attn.wo.bias"), residual=x)
+            x2 = self._linear(o, blk.P + "attn.wo.weight", blk.P + "attn.wo.bias", residual=x)
             x = self._ffn(blk, x2)
         cache.pos = S
         if lens is None:
@@ -248,13 +457,13 @@ class Generator:
         rope = cfg.pos == "rope"
         for li, blk in enumerate(self.blocks):
             h1 = self._norm(x, blk.w("attn_norm.weight"), blk.wb("attn_norm.bias"))
-            qkv, _ = ops.linear(h1, blk.w("attn.wqkv.weight"), blk.wb("attn.wqkv.bias"))
+            qkv = self._linear(h1, blk.P + "attn.wqkv.weight", blk.P + "attn.wqkv.bias")
             ops.rope_kv_append(qkv, blk.rope[0] if rope else None, blk.rope[1] if rope else None, cache.k[li],
                                cache.v[li], cache.positions, active, H, KV, Dh, rope=rope)
             o = torch.empty(B, H * Dh, device=x.device, dtype=x.dtype)
             ops.attn_decode(qkv[:, : H * Dh], cache.k[li], cache.v[li], cache.lens, o, H, KV, Dh,
                             max_len=cache.max_len)
-            x2, _ = ops.linear(o, blk.w("attn.wo.weight"), blk.wb("attn.wo.bias"), residual=x)
+            x2 = self._linear(o, blk.P + "attn.wo.weight", blk.P + "attn.wo.bias", residual=x)
             x = self._ffn(blk, x2)
         cache.pos += 1
         return self._head(x, out=out)
@@ -291,7 +500,7 @@ class Generator:
             cache.v[li][:, pos].copy_(v)
             o = torch.empty(B, H * Dh, device=x.device, dtype=x.dtype)
             ops.attn_decode(q, cache.k[li], cache.v[li], cache.lens, o, H, KV, Dh, max_len=pos + 1)
-            x2, _ = ops.linear(o, blk.w("attn.wo.weight"), blk.wb("attn.wo.bias"), residual=x)
+            x2 = self._linear(o, blk.P + "attn.wo.weight", blk.P + "attn.wo.bias", residual=x)
             x = self._ffn(blk, x2)
         cache.pos = pos + 1
         return self._head(x, out=out)
@@ -332,13 +541,13 @@ class Generator:
         rope = cfg.pos == "rope"
         for li, blk in enumerate(self.blocks):
             h1 = self._norm(x, blk.w("attn_norm.weight"), blk.wb("attn_norm.bias"))
-            qkv, _ = ops.linear(h1, blk.w("attn.wqkv.weight"), blk.wb("attn.wqkv.bias"))
+            qkv = self._linear(h1, blk.P + "attn.wqkv.weight", blk.P + "attn.wqkv.bias")
             ops.rope_kv_append(qkv, blk.rope[0] if rope else None, blk.rope[1] if rope else None, cache.k[li],
                                cache.v[li], base, None, H, KV, Dh, rope=rope, T=T, counts=cnt)
             o = torch.empty(B * T, H * Dh, device=x.device, dtype=x.dtype)
             ops.attn_append(qkv[:, : H * Dh], cache.k[li], cache.v[li], base, cnt, o, T, H, KV, Dh,
                             max_len=cache.pos + T)
-            x2, _ = ops.linear(o, blk.w("attn.wo.weight"), blk.wb("attn.wo.bias"), residual=x)
+            x2 = self._linear(o, blk.P + "attn.wo.weight", blk.P + "attn.wo.bias", residual=x)
             x = self._ffn(blk, x2)
         cache.lens.add_(T if cnt is None else cnt)
         cache.pos += T

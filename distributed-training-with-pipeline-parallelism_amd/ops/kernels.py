@@ -396,6 +396,126 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     return out, aux
 
 
+# ======================================================================================
+# int8 weight-only linear layers and the skinny-M kernel (csrc/kernels/gemv_skinny.hip)
+# ======================================================================================
+SKINNY_MAX_M = 16
+# linear_w8 runs the skinny kernel up to this many rows and dequantises above.  16 = one call
+# of the kernel; looping it over 16-row blocks has not been measured against the
+# dequantising route (tools/w8_time.py prints both, profiles/r12_w8_decode.md)
+W8_SKINNY_MAX_M = 16
+
+
+def quantize_w8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Symmetric per-output-row int8 quantisation of a 2-D weight ``w [N, K]`` (bf16 or f32):
+    ``scale[n] = max_k |w[n, k]| / 127`` (f32) and ``q[n, k] = clamp(round_half_even(w[n, k] /
+    scale[n]), -127, 127)`` (int8, [N, K] row-major: the tensor the kernel reads).  A row of
+    zeros gets scale 0 and q 0.  The effective weight is ``q * scale``.  Pure tensor code, the
+    same on every device."""
+    if w.dim() != 2:
+        raise ValueError("quantize_w8: w must be [N, K]")
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=1)
+    # a tensor divisor: dividing by a Python scalar is a multiplication by its reciprocal on
+    # the GPU, an ulp away from the CPU's quotient in some rows
+    scale = amax / torch.full_like(amax, 127.0)
+    safe = torch.where(scale > 0, scale, torch.ones_like(scale))
+    q = torch.round(wf / safe[:, None]).clamp_(-127, 127).to(torch.int8)
+    return q.contiguous(), scale.contiguous()
+
+
+def gemv_plan(N: int, K: int, wbytes: int, force_split: int = 0) -> Tuple[int, int]:
+    """(weight rows per workgroup, K-splits) of the skinny kernel for an [N, K] weight of
+    ``wbytes`` bytes per element (1: int8, 2: bf16): csrc/include/mp_gemv_plan.h.  Needs the
+    built extension, not a GPU."""
+    return tuple(_ext().gemv_plan(int(N), int(K), int(wbytes), int(force_split)))
+
+
+def _w8_epilogue_cpu(y, x, bias, act, residual, out):
+    if bias is not None:
+        y = y + bias.float()
+    if act != "none":
+        y = _act_cpu(y.to(x.dtype).float(), act)
+    if residual is not None:
+        y = y + residual.float()
+    out.copy_(y.to(out.dtype))
+    return out
+
+
+def _skinny_check(name, x, w, scale, bias, act, residual):
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"{name}: x [M, K] and w [N, K] needed, got {tuple(x.shape)} and {tuple(w.shape)}")
+    if (w.dtype == torch.int8) != (scale is not None):
+        raise ValueError(f"{name}: int8 weights take a scale, other weights none")
+    if act not in ("none", "gelu", "gelu_tanh"):
+        raise ValueError(f"{name}: activation {act!r} is not supported (none, gelu_tanh)")
+    if act != "none" and (bias is None or residual is not None):
+        raise ValueError(f"{name}: activation epilogue needs a bias and no residual")
+
+
+def linear_skinny(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                  bias: Optional[torch.Tensor] = None, act: str = "none", residual: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None, force_split: int = 0) -> torch.Tensor:
+    """y = act(x @ What^T + bias) (+ residual) for at most 16 rows of x, streaming the weight
+    matrix once.  ``w`` [N, K] is int8 with ``scale`` f32 [N] (What = w * scale, the scale
+    applied in f32 after the accumulation) or bf16 without.  ``x`` / ``out`` / ``residual`` are
+    bf16 rows of any stride; K must be a multiple of 32.  GELU rounds the pre-activation to
+    bf16 first, as :func:`linear` does.  Row m of the result does not depend on the number of
+    rows or on the other rows.  ``force_split``: the K-split of the plan, for tests.  No host
+    synchronisation and, given ``out``, no allocation.  Returns y."""
+    _skinny_check("linear_skinny", x, w, scale, bias, act, residual)
+    M, K = x.shape
+    N = w.shape[0]
+    if M < 1 or M > SKINNY_MAX_M:
+        raise ValueError(f"linear_skinny: M = {M} outside [1, {SKINNY_MAX_M}] (linear_w8 / linear take any M)")
+    if K % 32 != 0:
+        raise ValueError(f"linear_skinny: K = {K} must be a multiple of 32")
+    if out is None:
+        out = torch.empty(M, N, device=x.device, dtype=x.dtype)
+    if _gpu(x):
+        _ext().gemv_skinny(x, w, scale, out, bias, residual, act != "none", int(force_split))
+        return out
+    y = x.float() @ w.float().t()
+    if scale is not None:
+        y = y * scale.float()
+    return _w8_epilogue_cpu(y, x, bias, act, residual, out)
+
+
+def dequant_w8(q: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = (q * scale) rounded to out's dtype (bf16 on the GPU): the effective weight."""
+    if out is None:
+        out = torch.empty(q.shape, device=q.device, dtype=torch.bfloat16 if _gpu(q) else torch.float32)
+    if _gpu(q):
+        _ext().dequant_w8(q, scale, out)
+    else:
+        out.copy_((q.float() * scale.float()[:, None]).to(out.dtype))
+    return out
+
+
+def linear_w8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
+              act: str = "none", residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+              scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`linear` over int8 weights ``q`` [N, K] with ``scale`` [N], any number of rows.
+    Up to ``W8_SKINNY_MAX_M`` rows: the skinny kernel on ``q`` itself.  More rows (a prefill):
+    ``q * scale`` is written as bf16 into ``scratch`` (at least N * K elements; allocated
+    here if None) and the training GEMM runs on that.  Returns y."""
+    _skinny_check("linear_w8", x, q, scale, bias, act, residual)
+    M, K = x.shape
+    N = q.shape[0]
+    if not _gpu(x):
+        if out is None:
+            out = torch.empty(M, N, device=x.device, dtype=x.dtype)
+        return _w8_epilogue_cpu((x.float() @ q.float().t()) * scale.float(), x, bias, act, residual, out)
+    if M <= W8_SKINNY_MAX_M and K % 32 == 0:
+        return linear_skinny(x, q, scale, bias, act, residual, out)
+    if scratch is None:
+        scratch = torch.empty(N * K, device=x.device, dtype=torch.bfloat16)
+    if scratch.dtype != torch.bfloat16 or scratch.numel() < N * K or not scratch.is_contiguous():
+        raise ValueError(f"linear_w8: scratch must be contiguous bf16 with at least {N * K} elements")
+    w = dequant_w8(q, scale, scratch.view(-1)[: N * K].view(N, K))
+    return linear(x, w, bias, act=act, residual=residual, out=out)[0]
+
+
 def _act_cpu(x, act):
     if ACT[act] == 1:
         return torch.nn.functional.gelu(x, approximate="tanh")

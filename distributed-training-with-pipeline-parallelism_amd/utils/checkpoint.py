@@ -216,6 +216,26 @@ def load_weights(arenas, path: str, strict: bool = True) -> dict:
     return man
 
 
+def iter_weights(path: str, names):
+    """Yield ``(name, f32 master tensor on the CPU)`` for each FQN of ``names``, one tensor at
+    a time (a quantising loader never holds the whole model in f32).  Raises KeyError for a
+    name the checkpoint lacks."""
+    from safetensors import safe_open
+
+    man = read_manifest(path)
+    idx = _index(path, man)
+    missing = [n for n in names if n not in idx]
+    if missing:
+        raise KeyError(f"checkpoint {path} lacks {len(missing)} tensors, e.g. {missing[:4]}")
+    handles = {}
+    for name in names:
+        fn = idx[name]
+        if fn not in handles:
+            handles[fn] = safe_open(os.path.join(path, fn), framework="pt")
+        yield name, handles[fn].get_tensor(name)
+    handles.clear()
+
+
 # ----------------------------------------------------------------------------------------
 # reference layout interop (helper:36-46, :78-91): global FQNs, unpadded vocabulary
 # ----------------------------------------------------------------------------------------

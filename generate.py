@@ -7,6 +7,7 @@
         --temperature 0.8 --top-k 40 --top-p 0.9 --stop-token 0
     python generate.py --checkpoint DIR --draft-checkpoint SMALL_DIR --lookahead 4 \
         --prompt "1,2,3;7,8" --max-new-tokens 16
+    python generate.py --checkpoint DIR --weights int8 --prompt "1,2,3" --max-new-tokens 16
 
 The model configuration comes from the checkpoint's manifest; the weights are found by FQN,
 so a checkpoint written at any PP / DP degree loads into this single process.  Prompts are
@@ -23,6 +24,9 @@ padding is not printed.
 model over the same vocabulary drafts ``--lookahead`` tokens per round and the checkpoint's
 model verifies them in one pass.  The printed rows are the model's own greedy continuation;
 the acceptance rate goes to stderr.
+
+``--weights int8`` quantises the block matrices and the LM head per output row while loading
+(int8 weight-only inference; the draft of ``--draft-checkpoint`` follows ``--draft-weights``).
 """
 from __future__ import annotations
 
@@ -53,13 +57,16 @@ def main(argv=None) -> int:
                     "draft model (same vocabulary; greedy only)")
     ap.add_argument("--lookahead", type=int, default=4, help="tokens the draft proposes per round")
     ap.add_argument("--device", choices=("cpu", "cuda"), default=None, help="default: cuda when available")
+    ap.add_argument("--weights", choices=("bf16", "int8"), default="bf16", help="int8: weight-only quantisation of "
+                    "the block matrices and the LM head at load")
+    ap.add_argument("--draft-weights", choices=("bf16", "int8"), default="bf16", help="the same for the draft model")
     a = ap.parse_args(argv)
 
     import torch
     import mipipe
 
     rows = parse_prompts(a.prompt)
-    gen = mipipe.Generator.load(a.checkpoint, device=a.device)
+    gen = mipipe.Generator.load(a.checkpoint, device=a.device, weights=a.weights)
     bad = [t for r in rows for t in r if not 0 <= t < gen.cfg.vocab_size]
     if bad:
         raise ValueError(f"--prompt: token id {bad[0]} outside the vocabulary [0, {gen.cfg.vocab_size})")
@@ -67,7 +74,7 @@ def main(argv=None) -> int:
         if a.temperature != 0 or a.top_k is not None or a.top_p is not None or a.stop_token is not None:
             raise ValueError("--draft-checkpoint: speculative decoding is greedy only (no --temperature / --top-k / "
                              "--top-p / --stop-token)")
-        draft = mipipe.Generator.load(a.draft_checkpoint, device=gen.device, dtype=gen.dtype)
+        draft = mipipe.Generator.load(a.draft_checkpoint, device=gen.device, dtype=gen.dtype, weights=a.draft_weights)
         out, lengths, stats = gen.generate_speculative([torch.tensor(r, dtype=torch.int64) for r in rows],
                                                        a.max_new_tokens, draft, lookahead=a.lookahead,
                                                        pad_token=a.pad_token or 0)
