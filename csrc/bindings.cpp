@@ -12,6 +12,7 @@
 #include <optional>
 #include <string>
 
+#include "mp_attn_plan.h"
 #include "mp_gemm_plan.h"
 #include "mp_gemv_plan.h"
 
@@ -946,6 +947,43 @@ g2::Plan gemm2_plan(int64_t M, int64_t N, int64_t K, bool transA, bool transB, b
                        env.has_value() ? parsed : g2::PlanEnv::process(), mp_gemm2_has_probe_engines() != 0);
 }
 
+// What attn_fwd / attn_bwd will launch for a bf16 problem (mp_attn_plan.h): {"fwd": launch,
+// "bwd": [launch, ...]}, a launch being {"kernel", "dp", "grid", "lds"}.  env: the
+// MIPIPE_ATTN_* switches by name over their defaults; none: the process environment.
+pybind11::dict attn_plan(int64_t B, int64_t Sq, int64_t Sk, int64_t H, int64_t Hkv, int64_t D, int64_t qs, int64_t ks,
+                         int64_t vs, int64_t os, bool causal, bool drop, const std::optional<PlanEnvDict>& env) {
+  TORCH_CHECK(B > 0 && Sq > 0 && Sk > 0 && H > 0 && Hkv > 0 && D > 0, "attn_plan: sizes must be positive");
+  attn::AttnEnv parsed;
+  if (env.has_value()) {
+    for (const auto& kv : *env)
+      TORCH_CHECK(attn::AttnEnv::known(kv.first.c_str()), "attn_plan: ", kv.first, " is not an attention switch");
+    parsed = attn::AttnEnv::parse([&](const char* name) {
+      const auto it = env->find(name);
+      return it == env->end() ? (const char*)nullptr : it->second.c_str();
+    });
+  }
+  const attn::AttnEnv& e = env.has_value() ? parsed : attn::AttnEnv::process();
+  const attn::Launch f = attn::plan_attn_fwd((int)B, (int)Sq, (int)Sk, (int)H, (int)Hkv, (int)D, ks, vs, causal, drop, e);
+  const attn::BwdPlan b =
+      attn::plan_attn_bwd((int)B, (int)Sq, (int)Sk, (int)H, (int)Hkv, (int)D, qs, ks, vs, os, causal, drop, e);
+  TORCH_CHECK(f.kernel != attn::K_NONE && b.n > 0, "attn_plan: no kernel for D = ", D, ", H = ", H, ", Hkv = ", Hkv,
+              " (D a multiple of 8 up to 256, H a multiple of Hkv)");
+  const auto launch = [](const attn::Launch& l) {
+    pybind11::dict d;
+    d["kernel"] = attn::kernel_name(l.kernel);
+    d["dp"] = l.dp;
+    d["grid"] = pybind11::make_tuple(l.gx, l.gy);
+    d["lds"] = l.lds;
+    return d;
+  };
+  pybind11::list bwd;
+  for (int i = 0; i < b.n; ++i) bwd.append(launch(b.l[i]));
+  pybind11::dict out;
+  out["fwd"] = launch(f);
+  out["bwd"] = bwd;
+  return out;
+}
+
 // v2 engine (8 waves, glds staging).
 // returns 1 if done, 0 if the combination is not provided by v2 (caller uses gemm()),
 // 2 if done WITHOUT the requested fused column sums (caller sums separately)
@@ -1321,6 +1359,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      pybind11::arg("accum"), pybind11::arg("force_cfg"), pybind11::arg("env") = pybind11::none(),
      "engine config + split-K factor the v2 GEMM picks (14: stream-K gemm7); env: the MIPIPE_* planner "
      "switches as a dict over their defaults instead of the process environment");
+  m.def("attn_plan", &attn_plan, pybind11::arg("B"), pybind11::arg("Sq"), pybind11::arg("Sk"), pybind11::arg("H"),
+        pybind11::arg("Hkv"), pybind11::arg("D"), pybind11::arg("qs"), pybind11::arg("ks"), pybind11::arg("vs"),
+        pybind11::arg("os"), pybind11::arg("causal"), pybind11::arg("drop"), pybind11::arg("env") = pybind11::none(),
+        "kernels, grids and LDS bytes the bf16 attention launches; env: the MIPIPE_ATTN_* switches as a dict over "
+        "their defaults instead of the process environment");
   m.def("gemm_f32_plan", [](int64_t M, int64_t N, int64_t K, int64_t force_ks) {
     int split = 1, sk_grid = 0, sk_chunk = 0;
     const int big = mp_gemm_f32_plan((int)M, (int)N, (int)K, (int)force_ks, &split, &sk_grid, &sk_chunk);

@@ -1,4 +1,5 @@
-// Tile helpers shared by the flash-attention kernels (attention.hip, attention_doc.hip):
+// Tile helpers shared by the flash-attention kernels (attention.hip's kernel headers
+// mp_attn_fwd.h / mp_attn_bwd_*.h through mp_attn_common.h, attention_doc.hip, attention_append.hip):
 // the XOR-swizzled [rows][DP] bf16 LDS image, its row / transposed reads, the MFMA and
 // pack wrappers and the register staging of a 64-row global tile.
 #pragma once

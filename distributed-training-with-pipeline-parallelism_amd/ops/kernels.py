@@ -1061,6 +1061,17 @@ def _cpu_attn_drop(B, H, Sq, Sk, p, seed, device):
     return _cpu_dropout_mask((B, H, Sq, Sk), p, seed, device)
 
 
+def attn_plan(B: int, Sq: int, Sk: int, H: int, Hkv: int, D: int, qs: int, ks: int, vs: int, os: int, causal: bool,
+              drop: bool, env: Optional[dict] = None) -> dict:
+    """What the bf16 :func:`attn_fwd` / :func:`attn_bwd` launch for a problem with row strides
+    qs / ks / vs / os (elements) of q / k / v / o: ``{"fwd": launch, "bwd": [launch, ...]}``, a
+    launch being ``{"kernel", "dp", "grid": (x, y), "lds"}`` (csrc/include/mp_attn_plan.h).
+    ``env``: MIPIPE_ATTN_* switches over their defaults; None: the process environment.  Needs
+    the built extension, not a GPU."""
+    return _ext().attn_plan(int(B), int(Sq), int(Sk), int(H), int(Hkv), int(D), int(qs), int(ks), int(vs), int(os),
+                            bool(causal), bool(drop), env=env)
+
+
 def attn_fwd(q, k, v, o, lse, B: int, Sq: int, Sk: int, H: int, Hkv: int, D: int, causal: bool,
              scale: Optional[float] = None, p_drop: float = 0.0, seed: int = 0,
              doc_start: Optional[torch.Tensor] = None):

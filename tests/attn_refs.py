@@ -28,6 +28,7 @@ matters only for keys whose weight underflows (scores 87 below the row maximum).
 and reductions use the project's f32 metric, max |got - ref| / (|ref| + min(1, max |ref|)).
 """
 import math
+import re
 from types import SimpleNamespace as NS
 
 import torch
@@ -329,8 +330,9 @@ def env_flags(environ):
 
 
 def path(c, env=DEFAULT_ENV):
-    """(forward, backward) kernels the launchers at the bottom of attention.hip pick for this
-    case, as text: the same conditions, re-stated.  ``env``: the MIPIPE_ATTN_* switches."""
+    """(forward, backward) kernels the launch plan (csrc/include/mp_attn_plan.h) picks for this
+    case, as text: the same conditions, re-stated by hand and independently of it
+    (test_attn_plan_cpu.py holds the two against each other).  ``env``: the MIPIPE_ATTN_* switches."""
     B, Sq, Sk, H, Hkv, D = c.shape()
     if c.prec == "f32":
         return "f32", "f32"
@@ -355,6 +357,34 @@ def path(c, env=DEFAULT_ENV):
     else:
         dkdv = f"dkdv1dp{DP}"
     return fwd, dq + "+" + dkdv
+
+
+def path_kernels(p):
+    """the kernel names (mp_attn_plan.h) in a path() answer, forward first"""
+    labels = [p[0]] + (["short"] if p[1].startswith("short") else p[1].split("+"))
+    return [re.match(r"ks2|fwd[12]|short|dq[123]|dkdv[123]", x).group(0) for x in labels]
+
+
+def planned_kernels(plan):
+    """the same list from an ``ops.attn_plan`` answer"""
+    return [plan["fwd"]["kernel"]] + [l["kernel"] for l in plan["bwd"]]
+
+
+def plan_env(flags):
+    """env_flags form -> the ``env`` argument of ``ops.attn_plan``"""
+    return {"MIPIPE_ATTN_" + k: v for k, v in flags.items()}
+
+
+def case_strides(c):
+    """(qs, ks, vs, os): row strides of q / k / v / o as the case's layout places them, without
+    the GPU runner's few sentinel columns (the plan only asks whether (S + 128) * stride * 2
+    reaches 2^31): 'packed' has q | k | v side by side in one row, 'q_kv' k | v."""
+    wq, wk = c.H * c.D, c.Hkv * c.D
+    if c.layout == "bigstride":
+        return (BIG_STRIDE,) * 4
+    if c.layout == "packed":
+        return (wq + 2 * wk,) * 3 + (wq,)
+    return (wq, 2 * wk, 2 * wk, wq) if c.layout == "q_kv" else (wq, wk, wk, wq)
 
 
 def _cases():

@@ -209,6 +209,10 @@ def run_case(c, env=R.DEFAULT_ENV):
     path = R.path(c, env)
     rep = R.Report(f"{c.id} [{'+'.join(path)}]")
     L = Layout(c)
+    if c.prec == "bf16":   # the label this case's result is filed under is what will run
+        plan = ops.attn_plan(B, Sq, Sk, H, Hkv, D, *(t.stride(0) for t in (L.q, L.k, L.v, L.o)), c.causal, c.p > 0,
+                             env=R.plan_env(env))
+        assert R.planned_kernels(plan) == R.path_kernels(path), (c.id, path, plan)
     seed = 4321 + c.seed
     q, k, v, do = R.make_inputs(c)
     keep = recover_mask(c, L, seed, rep) if c.p else None

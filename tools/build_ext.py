@@ -80,9 +80,9 @@ def build(force: bool = False, jobs: int = 8, verbose: bool = False, variant: st
             jobs_list.append(base + FILE_FLAGS.get(os.path.basename(k), []) + ["-c", k, "-o", o])
     incs, tlib, abi = _torch_paths()
     # translation units that include torch: the pybind module, the native RCCL engine, the stage runner
-    # (bindings.cpp plans GEMMs with include/mp_gemm_plan.h and mp_gemv_plan.h)
-    host_hdrs = glob.glob(os.path.join(CSRC, "comm", "*.h")) + [os.path.join(CSRC, "include", "mp_gemm_plan.h"),
-                                                                os.path.join(CSRC, "include", "mp_gemv_plan.h")]
+    # (bindings.cpp plans GEMMs with include/mp_gemm_plan.h and mp_gemv_plan.h, attention with mp_attn_plan.h)
+    host_hdrs = glob.glob(os.path.join(CSRC, "comm", "*.h")) + [
+        os.path.join(CSRC, "include", h) for h in ("mp_gemm_plan.h", "mp_gemv_plan.h", "mp_attn_plan.h")]
     for bsrc in (os.path.join(CSRC, "bindings.cpp"), os.path.join(CSRC, "comm", "rccl_engine.cpp"),
                  os.path.join(CSRC, "runtime", "stage_runner.cpp")):
         bobj = os.path.join(OBJ, os.path.basename(bsrc) + ".o")
