@@ -31,6 +31,7 @@
 // the helpers of mp_attn_common.h and mp_attn_tiles.h (the LDS tile image, MFMA / pack
 // wrappers and Stage64, shared with attention_doc.hip).  Which kernel a problem runs, on
 // which grid and with how much LDS, is decided by mp_attn_plan.h.
+#include "mp_api.h"
 #include "mp_common.h"
 
 #include <type_traits>

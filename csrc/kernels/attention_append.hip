@@ -32,6 +32,7 @@
 // result: a lane whose key index is past the chunk's end re-reads the chunk's last valid row
 // (always inside the valid part of the cache), so no stale row reaches a register, and its
 // score is -inf.  No atomics: results are bit-identical from run to run.
+#include "mp_api.h"
 #include "mp_attn_split.h"
 #include "mp_attn_tiles.h"
 

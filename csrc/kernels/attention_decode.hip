@@ -22,6 +22,7 @@
 // index is past the end re-reads the chunk's last valid row (an address that is always
 // inside the valid part of the cache) and its score is set to -inf, so its weight is an
 // exact zero whatever the stale cache rows hold.
+#include "mp_api.h"
 #include "mp_attn_split.h"
 
 using namespace mp;

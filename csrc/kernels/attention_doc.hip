@@ -14,6 +14,7 @@
 // boundaries reaches the host or the grid, so a captured graph replays with new boundaries.
 // Every bound is clamped as it is loaded (doc_start[i] into [0, i], doc_end[j] into
 // [j, S-1]): array contents can change results, never an address.  No atomics.
+#include "mp_api.h"
 #include "mp_attn_tiles.h"
 
 #include <type_traits>

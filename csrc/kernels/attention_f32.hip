@@ -32,6 +32,7 @@
 // (L2-resident rows; 16-byte row chunks for A/B rows, 128-byte coalesced column slices for
 // the transposed A operands) -- no LDS staging, so LDS holds only the combine buffers.
 // H == Hkv only (the reference has no GQA).
+#include "mp_api.h"
 #include "mp_common.h"
 
 using namespace mp;

@@ -8,6 +8,7 @@
 //   swiglu_fwd/bwd  y = silu(gate) * up  over a [T, 2F] gate|up buffer (Llama-3 FFN)
 //   rope            rotate-half RoPE on the q/k heads of the packed qkv buffer, in place
 //                   (forward: +theta, backward: -theta), f32 cos/sin table from the host
+#include "mp_api.h"
 #include "mp_common.h"
 #include "mp_rope.h"
 

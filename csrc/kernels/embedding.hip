@@ -3,6 +3,7 @@
 // f32 atomics straight into the flat f32 gradient buffer, one 256-byte contiguous
 // wave-instruction per row segment (the shape that runs at the chip-wide atomic
 // rate on gfx950); a [T, D] gradient at D=768 is ~25 MB of adds -> ~20 us.
+#include "mp_api.h"
 #include "mp_common.h"
 
 using namespace mp;

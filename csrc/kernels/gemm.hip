@@ -17,6 +17,7 @@
 // buffer with register staging (global loads for k-tile t+1 in flight during the MFMAs of
 // tile t, one barrier per k-tile), XCD-aware + grouped block order, and an LDS-staged
 // epilogue so the bias / activation / residual / accumulate pass is fully coalesced.
+#include "mp_api.h"
 #include "mp_common.h"
 
 using namespace mp;

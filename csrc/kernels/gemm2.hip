@@ -20,6 +20,7 @@
 #include <climits>
 #include <type_traits>
 
+#include "mp_api.h"
 #include "mp_gemm_core.h"
 #include "mp_gemm_tiles.h"
 #include "mp_gemm_pingpong.h"

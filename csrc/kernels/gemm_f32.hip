@@ -30,6 +30,7 @@
 //    workgroups into f32 slabs, summed by one reduce + epilogue pass -- deterministic.
 #include <cstdlib>
 
+#include "mp_api.h"
 #include "mp_common.h"
 
 using namespace mp;

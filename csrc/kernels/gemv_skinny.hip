@@ -16,6 +16,7 @@
 // its own K-steps for all G row groups (one x fragment per step serves them all), writes its
 // f32 tile to LDS, and wave 0 adds the tiles of waves 1, 2, ... in that order, applies
 // scale / bias / GELU / residual in f32 and stores bf16.  No atomics, no second launch.
+#include "mp_api.h"
 #include "mp_common.h"
 #include "mp_gemv_plan.h"
 

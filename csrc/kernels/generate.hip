@@ -35,6 +35,7 @@
 // so 3 passes for plain temperature sampling and at most 20 with both filters.  Every sum is
 // sequential inside a thread's block, then a fixed shuffle tree over the wave and a fixed
 // sequential sum over the 16 waves: bit-identical from run to run.  No atomics.
+#include "mp_api.h"
 #include "mp_common.h"
 #include "mp_rope.h"
 

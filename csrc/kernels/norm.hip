@@ -14,6 +14,7 @@
 //     dw += sum_rows(dy * xhat), dbias += sum_rows(dy): per-block partials in
 //     registers, reduced across the block's waves in LDS, one f32 atomic per column.
 // SURVEY §2.5 K7 (post-LN: 3 per layer + final) and the pre-norm GPT-2 / Llama blocks.
+#include "mp_api.h"
 #include "mp_common.h"
 
 #include <stdlib.h>

@@ -7,6 +7,7 @@
 // (no separate zero_grad / cast kernels).  The clip factor is computed on device and
 // read by the AdamW kernel from device memory: no host sync.  Weight decay applies
 // to elements [0, n_decay) (the arena orders decayed tensors first).
+#include "mp_api.h"
 #include "mp_common.h"
 
 using namespace mp;

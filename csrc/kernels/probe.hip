@@ -17,6 +17,7 @@
 // deadline, so the probe can never hang the device.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mp_api.h"
 
 namespace {
 

@@ -10,6 +10,7 @@
 // ignore_index produce zero loss and zero gradient.
 #include <cstdlib>
 
+#include "mp_api.h"
 #include "mp_common.h"
 
 using namespace mp;

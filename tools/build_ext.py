@@ -7,8 +7,10 @@
 
 
 Each ``csrc/kernels/*.hip`` is compiled by ``hipcc --offload-arch=gfx950`` into an
-object (plain HIP, no torch headers: seconds per file); ``csrc/bindings.cpp`` is the only
-translation unit that includes torch.  Everything links into
+object (plain HIP, no torch headers: seconds per file).  The translation units that include
+torch are ``csrc/bindings/*.cpp`` (one per kernel family; ``csrc/include/mp_api.h`` declares the
+C launchers they call), the native RCCL engine and the stage runner; they compile in the same
+thread pool.  Everything links into
 ``distributed-training-with-pipeline-parallelism_amd/_C.so`` against the libtorch /
 HIP runtime that ships with the installed PyTorch, so the built file travels with the
 repo snapshot to a GPU box.  Objects are rebuilt only when a source or header is newer.
@@ -79,12 +81,11 @@ def build(force: bool = False, jobs: int = 8, verbose: bool = False, variant: st
         if force or _newer([k] + headers, o):
             jobs_list.append(base + FILE_FLAGS.get(os.path.basename(k), []) + ["-c", k, "-o", o])
     incs, tlib, abi = _torch_paths()
-    # translation units that include torch: the pybind module, the native RCCL engine, the stage runner
-    # (bindings.cpp plans GEMMs with include/mp_gemm_plan.h and mp_gemv_plan.h, attention with mp_attn_plan.h)
-    host_hdrs = glob.glob(os.path.join(CSRC, "comm", "*.h")) + [
-        os.path.join(CSRC, "include", h) for h in ("mp_gemm_plan.h", "mp_gemv_plan.h", "mp_attn_plan.h")]
-    for bsrc in (os.path.join(CSRC, "bindings.cpp"), os.path.join(CSRC, "comm", "rccl_engine.cpp"),
-                 os.path.join(CSRC, "runtime", "stage_runner.cpp")):
+    # translation units that include torch: the bindings, the native RCCL engine, the stage runner;
+    # each depends on every header it could include
+    host_hdrs = headers + glob.glob(os.path.join(CSRC, "bindings", "*.h")) + glob.glob(os.path.join(CSRC, "comm", "*.h"))
+    for bsrc in sorted(glob.glob(os.path.join(CSRC, "bindings", "*.cpp"))) + [
+            os.path.join(CSRC, "comm", "rccl_engine.cpp"), os.path.join(CSRC, "runtime", "stage_runner.cpp")]:
         bobj = os.path.join(OBJ, os.path.basename(bsrc) + ".o")
         objs.append(bobj)
         if force or _newer([bsrc] + host_hdrs, bobj):
