@@ -218,7 +218,8 @@ void transpose_batched(torch::Tensor src, torch::Tensor dst, torch::Tensor desc,
 }
 
 // y[M, N] = epi(x[M, K] @ What^T), M <= 16 (csrc/kernels/gemv_skinny.hip): w int8 [N, K] with scale f32 [N],
-// or w bf16 [N, K] without.  No allocation, no synchronisation.
+// w uint8 [N, K / 2] (packed 4-bit) with scale f32 [K / 128, N], or w bf16 [N, K] without.  No allocation, no
+// synchronisation.
 void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> scale, torch::Tensor y,
                  c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, bool gelu,
                  int64_t force_split) {
@@ -231,18 +232,27 @@ void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> 
   rows(x, "gemv_skinny: x");
   rows(y, "gemv_skinny: y");
   TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous(), "gemv_skinny: w must be a contiguous [N, K] GPU matrix");
-  const bool w8 = w.scalar_type() == torch::kInt8;
-  TORCH_CHECK(w8 || w.scalar_type() == torch::kBFloat16, "gemv_skinny: w must be int8 or bf16, got ", w.scalar_type());
-  TORCH_CHECK(w8 == scale.has_value(), "gemv_skinny: int8 weights take a scale, bf16 weights none");
+  const bool w8 = w.scalar_type() == torch::kInt8, w4 = w.scalar_type() == torch::kUInt8;
+  TORCH_CHECK(w8 || w4 || w.scalar_type() == torch::kBFloat16, "gemv_skinny: w must be int8, uint8 (packed 4-bit) or bf16, got ",
+              w.scalar_type());
+  TORCH_CHECK((w8 || w4) == scale.has_value(), "gemv_skinny: int8 and 4-bit weights take a scale, bf16 weights none");
+  const int code = w4 ? 0 : w8 ? 1 : 2;
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(M >= 1 && M <= gemv::MAX_M, "gemv_skinny: M = ", M, " outside [1, ", gemv::MAX_M, "]");
-  TORCH_CHECK(w.size(1) == K && y.size(0) == M && y.size(1) == N, "gemv_skinny: shapes x ", x.sizes(), " w ", w.sizes(), " y ", y.sizes());
-  TORCH_CHECK(gemv::plan(N, K, w8 ? 1 : 2, (int)force_split).rows != 0, "gemv_skinny: N = ", N, ", K = ", K,
-              ", force_split = ", force_split, " is not supported (K a multiple of 32, force_split <= 16)");
+  TORCH_CHECK(w.size(1) * (w4 ? 2 : 1) == K && y.size(0) == M && y.size(1) == N, "gemv_skinny: shapes x ", x.sizes(), " w ",
+              w.sizes(), " y ", y.sizes());
+  TORCH_CHECK(gemv::plan(N, K, code, (int)force_split).rows != 0, "gemv_skinny: N = ", N, ", K = ", K,
+              ", force_split = ", force_split, " is not supported (K a multiple of 32, of 128 for 4-bit weights; "
+              "force_split <= 16)");
   TORCH_CHECK(aligned16(w), "gemv_skinny: w must be 16-byte aligned");
   if (w8) {
     req(*scale, torch::kFloat32, "gemv_skinny: scale");
     TORCH_CHECK(scale->numel() == N && scale->is_contiguous(), "gemv_skinny: scale must hold N contiguous values");
+  }
+  if (w4) {
+    req(*scale, torch::kFloat32, "gemv_skinny: scale");
+    TORCH_CHECK(scale->dim() == 2 && scale->size(0) == K / gemv::KSTEP && scale->size(1) == N && scale->is_contiguous(),
+                "gemv_skinny: the scale of 4-bit weights must be contiguous [K / 128, N]");
   }
   if (bias.has_value()) {
     req(*bias, torch::kBFloat16, "gemv_skinny: bias");
@@ -256,16 +266,28 @@ void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> 
     TORCH_CHECK(residual->size(0) == M && residual->size(1) == N, "gemv_skinny: residual must be [M, N]");
     ldr = residual->stride(0);
   }
-  check(mp_gemv_skinny(w.data_ptr(), w8 ? scale->data_ptr<float>() : nullptr, w8 ? 1 : 2, x.data_ptr(), y.data_ptr(),
+  check(mp_gemv_skinny(w.data_ptr(), code != 2 ? scale->data_ptr<float>() : nullptr, code, x.data_ptr(), y.data_ptr(),
                        ptr_or_null(bias), ptr_or_null(residual), (int)M, (int)N, (int)K, x.stride(0), y.stride(0), ldr,
                        gelu ? 1 : 0, (int)force_split, cur_stream()),
         "gemv_skinny");
 }
 
+// q int8 [N, K] with scale [N], or q uint8 [N, K / 2] (packed 4-bit) with scale [K / 128, N]
 void dequant_w8(torch::Tensor q, torch::Tensor scale, torch::Tensor out) {
-  req(q, torch::kInt8, "dequant_w8: q");
   req(scale, torch::kFloat32, "dequant_w8: scale");
   req(out, torch::kBFloat16, "dequant_w8: out");
+  if (q.scalar_type() == torch::kUInt8) {
+    req(q, torch::kUInt8, "dequant_w8: q");
+    TORCH_CHECK(q.dim() == 2 && q.is_contiguous() && out.is_contiguous() && out.numel() == 2 * q.numel(),
+                "dequant_w8: packed 4-bit q [N, K / 2] and out [N, K], both contiguous");
+    const int64_t N = q.size(0), K = 2 * q.size(1);
+    TORCH_CHECK(K >= 128 && K % 128 == 0, "dequant_w8: K = ", K, " must be a multiple of 128 for 4-bit weights");
+    TORCH_CHECK(scale.is_contiguous() && scale.dim() == 2 && scale.size(0) == K / 128 && scale.size(1) == N,
+                "dequant_w8: the scale of 4-bit weights must be contiguous [K / 128, N]");
+    check(mp_dequant_w4(q.data_ptr(), scale.data_ptr<float>(), out.data_ptr(), N, K, cur_stream()), "dequant_w8 (4-bit)");
+    return;
+  }
+  req(q, torch::kInt8, "dequant_w8: q");
   TORCH_CHECK(q.dim() == 2 && q.is_contiguous() && out.is_contiguous() && out.numel() == q.numel() &&
                   scale.is_contiguous() && scale.numel() == q.size(0),
               "dequant_w8: q [N, K], scale [N], out [N, K], all contiguous");

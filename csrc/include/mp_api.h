@@ -73,6 +73,7 @@ int mp_gemv_skinny(const void* w, const float* scale, int wbytes, const void* x,
                    const void* res, int M, int N, int K, int64_t ldx, int64_t ldy, int64_t ldr, int gelu,
                    int force_split, hipStream_t st);
 int mp_dequant_w8(const void* q, const float* scale, void* out, int64_t N, int64_t K, hipStream_t st);
+int mp_dequant_w4(const void* q, const float* scale, void* out, int64_t N, int64_t K, hipStream_t st);
 // ---- gemm_f32.hip.  a_kc / b_kc / b_nc: which stride of the operand is 1 (K- or N-contiguous);
 // both GEMMs return -1 for a layout they do not provide.
 int mp_gemm_f32(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int64_t lda,

@@ -32,7 +32,10 @@ int8 weight-only inference (``Generator(..., weights="int8")``, :class:`QuantWei
 block matrices and the LM head are held as int8 with one f32 scale per output row and no
 training state, and linear layers of at most 16 rows stream them through
 csrc/kernels/gemv_skinny.hip (:func:`ops.linear_w8`); ``skinny=True`` runs bf16 weights
-through the same kernel.  Every mode above works on either kind of generator.
+through the same kernel.  ``weights="int4g128"`` holds the same matrices as packed 4-bit
+values with one f32 scale per 128-element group of K (:func:`ops.quantize_w4`,
+:func:`ops.linear_w4`): half the streamed bytes again.  Every mode above works on every kind
+of generator.
 """
 from __future__ import annotations
 
@@ -105,6 +108,7 @@ class KVCache:
 
 
 QUANTIZED = ("attn.wqkv.weight", "attn.wo.weight", "ffn.w1.weight", "ffn.w2.weight", "ffn.w13.weight")
+QUANT_FORMATS = ("int8", "int4g128")
 
 
 def model_param_specs(cfg: NativeConfig) -> List[ParamSpec]:
@@ -134,9 +138,16 @@ class QuantWeights:
     biases as ``dtype`` tensors.  With tied embeddings the head is an int8 copy of the token
     table (``q["tok_embeddings.weight"]``) beside the table itself.  There is no f32 master, no
     gradient, no transposed copy and no dense copy of a quantised matrix.  ``w`` / ``has``
-    answer as the arena does for the dense tensors."""
+    answer as the arena does for the dense tensors.
 
-    def __init__(self, cfg: NativeConfig, device, dtype=torch.bfloat16):
+    ``fmt="int4g128"``: ``q[name]`` is packed uint8 [N, K / 2] and ``scale[name]`` f32
+    [K / 128, N], the format of :func:`ops.quantize_w4`; every quantised matrix needs
+    ``K % 128 == 0`` (checked here, before anything is stored)."""
+
+    def __init__(self, cfg: NativeConfig, device, dtype=torch.bfloat16, fmt: str = "int8"):
+        if fmt not in QUANT_FORMATS:
+            raise ValueError(f"QuantWeights: format must be one of {QUANT_FORMATS}, got {fmt!r}")
+        self.fmt = fmt
         self.cfg = cfg
         self.device = torch.device(device)
         self.dtype = dtype
@@ -147,6 +158,12 @@ class QuantWeights:
         self.q: Dict[str, torch.Tensor] = {}
         self.scale: Dict[str, torch.Tensor] = {}
         self.dense: Dict[str, torch.Tensor] = {}
+        if fmt == "int4g128":
+            bad = [(n, self.specs[n].shape) for n in self.order
+                   if self.quantized(n) and self.specs[n].shape[1] % ops.W4_GROUP != 0]
+            if bad:
+                raise ValueError(f"QuantWeights: int4g128 needs K % {ops.W4_GROUP} == 0 in every quantised matrix; "
+                                 f"{bad[0][0]} is {tuple(bad[0][1])}")
 
     def quantized(self, name: str) -> bool:
         return name == self.head_name or name.endswith(QUANTIZED)
@@ -166,7 +183,7 @@ class QuantWeights:
         s = self.specs[name]
         t = t.detach().float().reshape(s.shape)
         if self.quantized(name):
-            q, scale = ops.quantize_w8(t)
+            q, scale = ops.quantize_w4(t) if self.fmt == "int4g128" else ops.quantize_w8(t)
             self.q[name], self.scale[name] = q.to(self.device), scale.to(self.device)
         # dense: everything but the block matrices and an untied head (a tied head is also
         # the embedding table, which stays dense)
@@ -194,24 +211,30 @@ class QuantWeights:
         for n in self.order:
             self.put(n, sd[n])
 
+    def _what(self, n: str) -> torch.Tensor:
+        if self.fmt == "int4g128":
+            return ops.dequant_w4(self.q[n].cpu(), self.scale[n].cpu())
+        return (self.q[n].float() * self.scale[n][:, None]).cpu()
+
     def effective_state_dict(self) -> Dict[str, torch.Tensor]:
         """f32 CPU tensors by FQN of the weights this generator computes with: ``q * scale``
-        for the quantised matrices (also for the head of an untied model), the stored values
-        otherwise.  With tied embeddings ``tok_embeddings.weight`` is the embedding table and
+        (per row, or per group of 128 k for int4g128) for the quantised matrices (also for
+        the head of an untied model), the stored values otherwise.  With tied embeddings ``tok_embeddings.weight`` is the embedding table and
         the head's effective weight is under ``"lm_head"``."""
         out = {}
         for n in self.order:
             if n in self.dense:
                 out[n] = self.dense[n].detach().float().cpu()
             else:
-                out[n] = (self.q[n].float() * self.scale[n][:, None]).cpu()
+                out[n] = self._what(n)
         if self.cfg.tie_embeddings:
-            n = self.head_name
-            out["lm_head"] = (self.q[n].float() * self.scale[n][:, None]).cpu()
+            out["lm_head"] = self._what(self.head_name)
         return out
 
     def max_matrix_numel(self) -> int:
-        return max(q.numel() for q in self.q.values())
+        """N * K of the largest quantised matrix: what the dequantisation scratch must hold (a
+        packed 4-bit tensor has half as many elements)"""
+        return max(self.specs[n].shape[0] * self.specs[n].shape[1] for n in self.q)
 
 
 class _QBlock:
@@ -231,10 +254,11 @@ class _QBlock:
 
 
 def _check_weights(weights: str, skinny: bool) -> None:
-    if weights not in ("bf16", "int8"):
-        raise ValueError(f"Generator: weights must be 'bf16' or 'int8', got {weights!r}")
+    if weights != "bf16" and weights not in QUANT_FORMATS:
+        raise ValueError(f"Generator: weights must be 'bf16', 'int8' or 'int4g128', got {weights!r}")
     if skinny and weights != "bf16":
-        raise ValueError("Generator: skinny=True is the bf16 weights' opt-in (int8 weights always use the skinny kernel)")
+        raise ValueError("Generator: skinny=True is the bf16 weights' opt-in (quantised weights always use the skinny "
+                         "kernel)")
 
 
 class Generator:
@@ -246,7 +270,9 @@ class Generator:
     and its arena (``self.model`` is None).  Linear layers of at most ``ops.W8_SKINNY_MAX_M``
     rows read the int8 matrix directly (:func:`ops.linear_skinny`); larger ones (a prefill)
     dequantise into one scratch matrix, allocated on the first call that needs it.  GELU /
-    SwiGLU models only.  ``skinny=True`` (bf16 weights on the GPU only): linear layers of at
+    SwiGLU models only.  ``weights="int4g128"``: the same with 4-bit values and one scale per
+    128-element group of K (:func:`ops.quantize_w4`, :func:`ops.linear_w4`); every quantised
+    matrix then needs ``K % 128 == 0``.  ``skinny=True`` (bf16 weights on the GPU only): linear layers of at
     most 16 rows run the bf16 instantiation of the same kernel instead of the training GEMM."""
 
     def __init__(self, cfg: NativeConfig, device, dtype=torch.bfloat16, seed: int = 0, init: bool = True,
@@ -254,8 +280,8 @@ class Generator:
         _check_generative(cfg)
         _check_weights(weights, skinny)
         cfg = dataclasses.replace(cfg, dropout=0.0)
-        if weights == "int8":
-            qw = QuantWeights(cfg, device, dtype)
+        if weights != "bf16":
+            qw = QuantWeights(cfg, device, dtype, weights)
             if init:
                 qw.init_params(seed)
             self._bind_quant(qw)
@@ -285,7 +311,7 @@ class Generator:
         if cfg.pos == "rope":
             rope = ops.rope_tables(cfg.max_seq_len, cfg.head_dim, cfg.rope_theta, self.device)
         self.blocks = [_QBlock(i, qw, rope) for i in range(cfg.n_layers)]
-        self.weights = "int8"
+        self.weights = qw.fmt
         self.skinny = False
         self._scratch: Optional[torch.Tensor] = None
 
@@ -294,7 +320,7 @@ class Generator:
     def from_model(cls, model: NativeModel, weights: str = "bf16", skinny: bool = False) -> "Generator":
         """Wrap an existing single-stage model (``trainer.stages[0].model`` at ``pp = 1``).
         With bf16 weights they are the model's arena itself: nothing is copied, and a later
-        optimizer step is seen by the generator.  ``weights="int8"`` takes a quantised
+        optimizer step is seen by the generator.  ``weights="int8"`` / ``"int4g128"`` take a quantised
         snapshot of the master weights instead: the model is left untouched, and the
         generator does NOT see later optimizer steps (build a new one after training on)."""
         _check_generative(model.cfg)
@@ -302,8 +328,8 @@ class Generator:
         if model.num_stages != 1 or model.split_head:
             raise ValueError("Generator.from_model needs a single-stage model that owns its LM head (pp = 1)")
         self = cls.__new__(cls)
-        if weights == "int8":
-            qw = QuantWeights(dataclasses.replace(model.cfg, dropout=0.0), model.device, model.arena.dtype)
+        if weights != "bf16":
+            qw = QuantWeights(dataclasses.replace(model.cfg, dropout=0.0), model.device, model.arena.dtype, weights)
             with model.arena.unsharded():
                 for n in qw.order:
                     qw.put(n, model.arena.master_view(n))
@@ -317,8 +343,8 @@ class Generator:
     def load(cls, path: str, device=None, dtype=None, weights: str = "bf16", skinny: bool = False) -> "Generator":
         """Weights-only load of a checkpoint directory written by ``save_checkpoint`` at any
         PP / DP degree or head mode (the tensors are found by FQN).  Defaults: the GPU in
-        bf16 when there is one, else the CPU in f32.  ``weights="int8"`` quantises tensor by
-        tensor while loading (deterministic: the same checkpoint gives the same int8 values)."""
+        bf16 when there is one, else the CPU in f32.  ``weights="int8"`` / ``"int4g128"`` quantise
+        tensor by tensor while loading (deterministic: the same checkpoint gives the same values)."""
         from ..utils.checkpoint import iter_weights, load_weights, read_manifest
         man = read_manifest(path)
         cfg = NativeConfig(**man["model"])
@@ -328,7 +354,7 @@ class Generator:
         if dtype is None:
             dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
         self = cls(cfg, device, dtype=dtype, init=False, weights=weights, skinny=skinny)
-        if weights == "int8":
+        if weights != "bf16":
             for name, t in iter_weights(path, self.arena.order):
                 self.arena.put(name, t)
             return self
@@ -340,18 +366,19 @@ class Generator:
                 residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         A = self.arena
         bias = A.w(bname) if bname is not None and A.has(bname) else None
-        if self.weights == "int8":
+        if self.weights != "bf16":
             key = A.head_name if wname == "lm_head" else wname
             q, scale = A.q[key], A.scale[key]
+            w4 = self.weights == "int4g128"
             scratch = None
-            if x.is_cuda and (x.shape[0] > ops.W8_SKINNY_MAX_M or q.shape[1] % 32 != 0):
+            if x.is_cuda and (x.shape[0] > ops.W8_SKINNY_MAX_M or (not w4 and q.shape[1] % 32 != 0)):
                 if self._scratch is None:
                     if torch.cuda.is_current_stream_capturing():
                         raise RuntimeError("Generator: the dequantisation scratch cannot be allocated inside a graph "
                                            "capture (run one step eagerly first)")
                     self._scratch = torch.empty(A.max_matrix_numel(), device=self.device, dtype=torch.bfloat16)
                 scratch = self._scratch
-            return ops.linear_w8(x, q, scale, bias, act, residual, out, scratch=scratch)
+            return (ops.linear_w4 if w4 else ops.linear_w8)(x, q, scale, bias, act, residual, out, scratch=scratch)
         w = self.model.head_weight() if wname == "lm_head" else A.w(wname)
         if self.skinny and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[0] <= ops.SKINNY_MAX_M \
                 and w.shape[1] % 32 == 0 and act in ("none", "gelu", "gelu_tanh"):

@@ -426,8 +426,9 @@ def quantize_w8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
 
 def gemv_plan(N: int, K: int, wbytes: int, force_split: int = 0) -> Tuple[int, int]:
     """(weight rows per workgroup, K-splits) of the skinny kernel for an [N, K] weight of
-    ``wbytes`` bytes per element (1: int8, 2: bf16): csrc/include/mp_gemv_plan.h.  Needs the
-    built extension, not a GPU."""
+    ``wbytes`` bytes per element (1: int8, 2: bf16; the code 0: packed 4-bit with group
+    scales, which needs ``K % 128 == 0``): csrc/include/mp_gemv_plan.h.  Needs the built
+    extension, not a GPU."""
     return tuple(_ext().gemv_plan(int(N), int(K), int(wbytes), int(force_split)))
 
 
@@ -513,6 +514,129 @@ def linear_w8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, bias: Optio
     if scratch.dtype != torch.bfloat16 or scratch.numel() < N * K or not scratch.is_contiguous():
         raise ValueError(f"linear_w8: scratch must be contiguous bf16 with at least {N * K} elements")
     w = dequant_w8(q, scale, scratch.view(-1)[: N * K].view(N, K))
+    return linear(x, w, bias, act=act, residual=residual, out=out)[0]
+
+
+# ======================================================================================
+# int4g128: 4-bit weights with one f32 scale per 128-element group of K, on the same kernel
+# ======================================================================================
+W4_GROUP = 128
+
+
+def quantize_w4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Symmetric 4-bit quantisation of a 2-D weight ``w [N, K]`` (bf16 or f32) with one scale
+    per 128-element group of K (``K % 128 == 0``, else ValueError) -> ``(q4, scale)``:
+
+    * ``scale[g, n] = max_{k in [128 g, 128 g + 128)} |w[n, k]| / 7``, f32 ``[K / 128, N]``
+      contiguous (group-major: the four output rows a lane of the kernel owns are 16
+      contiguous bytes).  A group of zeros has scale 0 and q 0.
+    * ``q[n, k] = clamp(round_half_even(w[n, k] / scale[k // 128, n]), -7, 7)``.
+    * ``q4`` is uint8 ``[N, K / 2]`` row-major: byte ``b`` of a row holds ``q[n, 2 b] + 8`` in
+      its low nibble and ``q[n, 2 b + 1] + 8`` in its high nibble.  Nibble 0 is never written
+      here, but every consumer decodes all 16 values as ``nibble - 8``, so it means -8.
+
+    The effective weight is ``What[n, k] = q[n, k] * scale[k // 128, n]``.  Pure tensor code,
+    the same values on every device."""
+    if w.dim() != 2:
+        raise ValueError("quantize_w4: w must be [N, K]")
+    N, K = w.shape
+    if K < W4_GROUP or K % W4_GROUP != 0:
+        raise ValueError(f"quantize_w4: K = {K} must be a multiple of {W4_GROUP}")
+    wf = w.detach().float().reshape(N, K // W4_GROUP, W4_GROUP)
+    amax = wf.abs().amax(dim=2)                                     # [N, G]
+    # a tensor divisor, as in quantize_w8: the same quotient on the CPU and the GPU
+    scale = amax / torch.full_like(amax, 7.0)
+    safe = torch.where(scale > 0, scale, torch.ones_like(scale))
+    q = torch.round(wf / safe[:, :, None]).clamp_(-7, 7).to(torch.int16).reshape(N, K) + 8
+    q4 = (q[:, 0::2] | (q[:, 1::2] << 4)).to(torch.uint8)
+    return q4.contiguous(), scale.t().contiguous()
+
+
+def _w4_check(name, x, q4, scale):
+    if q4.dtype != torch.uint8 or q4.dim() != 2 or x.dim() != 2 or x.shape[1] != 2 * q4.shape[1]:
+        raise ValueError(f"{name}: x [M, K] and packed uint8 q4 [N, K / 2] needed, got {tuple(x.shape)} and "
+                         f"{q4.dtype} {tuple(q4.shape)}")
+    N, K = q4.shape[0], 2 * q4.shape[1]
+    if K % W4_GROUP != 0:
+        raise ValueError(f"{name}: K = {K} must be a multiple of {W4_GROUP}")
+    if scale is None or scale.dim() != 2 or tuple(scale.shape) != (K // W4_GROUP, N):
+        raise ValueError(f"{name}: scale must be [K / 128, N] = [{K // W4_GROUP}, {N}]")
+
+
+def _w4_unpack(q4: torch.Tensor) -> torch.Tensor:
+    """q [N, K] f32 of packed nibbles: nibble - 8, all 16 values"""
+    b = q4.to(torch.int16)
+    return (torch.stack((b & 15, b >> 4), dim=2).reshape(q4.shape[0], -1) - 8).float()
+
+
+def _w4_matmul_cpu(x, q4, scale):
+    """sum_g scale[g, n] * (sum_{k in g} x[m, k] q[n, k]) in f32: the kernel's order of scaling"""
+    M, K = x.shape
+    N, G = q4.shape[0], K // W4_GROUP
+    part = torch.einsum("mgk,ngk->mng", x.float().reshape(M, G, W4_GROUP), _w4_unpack(q4).reshape(N, G, W4_GROUP))
+    return (part * scale.float().t()[None]).sum(dim=2)
+
+
+def dequant_w4(q4: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [N, K] = (q * scale per group) rounded to out's dtype (bf16 on the GPU): the
+    effective weight of :func:`quantize_w4`'s format."""
+    N, K = q4.shape[0], 2 * q4.shape[1]
+    if q4.dtype != torch.uint8 or K % W4_GROUP != 0 or tuple(scale.shape) != (K // W4_GROUP, N):
+        raise ValueError(f"dequant_w4: packed uint8 q4 [N, K / 2] with K % 128 == 0 and scale [K / 128, N] needed, got "
+                         f"{q4.dtype} {tuple(q4.shape)} and {tuple(scale.shape)}")
+    if out is None:
+        out = torch.empty(N, K, device=q4.device, dtype=torch.bfloat16 if _gpu(q4) else torch.float32)
+    if _gpu(q4):
+        _ext().dequant_w8(q4, scale, out)
+    else:
+        out.copy_((_w4_unpack(q4) * scale.float().t().repeat_interleave(W4_GROUP, dim=1)).to(out.dtype))
+    return out
+
+
+def linear_skinny_w4(x: torch.Tensor, q4: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                     act: str = "none", residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                     force_split: int = 0) -> torch.Tensor:
+    """:func:`linear_skinny` over int4g128 weights (:func:`quantize_w4`): ``q4`` uint8
+    [N, K / 2], ``scale`` f32 [K / 128, N], at most 16 rows of x.  Each group's f32 sum is
+    multiplied by its scale in f32 and the groups are added in f32.  Everything else --
+    strides, GELU rounding, row independence, ``force_split``, no synchronisation, no
+    allocation given ``out`` -- is as in :func:`linear_skinny`.  Returns y."""
+    _w4_check("linear_skinny_w4", x, q4, scale)
+    _skinny_check("linear_skinny_w4", x, x, None, bias, act, residual)
+    M, K = x.shape
+    N = q4.shape[0]
+    if M < 1 or M > SKINNY_MAX_M:
+        raise ValueError(f"linear_skinny_w4: M = {M} outside [1, {SKINNY_MAX_M}] (linear_w4 takes any M)")
+    if out is None:
+        out = torch.empty(M, N, device=x.device, dtype=x.dtype)
+    if _gpu(x):
+        _ext().gemv_skinny(x, q4, scale, out, bias, residual, act != "none", int(force_split))
+        return out
+    return _w8_epilogue_cpu(_w4_matmul_cpu(x, q4, scale), x, bias, act, residual, out)
+
+
+def linear_w4(x: torch.Tensor, q4: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
+              act: str = "none", residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+              scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`linear` over int4g128 weights, any number of rows.  Up to ``W8_SKINNY_MAX_M``
+    rows: the skinny kernel on ``q4`` itself.  More rows (a prefill): the effective weight is
+    written as bf16 into ``scratch`` (at least N * K elements; allocated here if None) and
+    the training GEMM runs on that.  Returns y."""
+    _w4_check("linear_w4", x, q4, scale)
+    _skinny_check("linear_w4", x, x, None, bias, act, residual)
+    M, K = x.shape
+    N = q4.shape[0]
+    if not _gpu(x):
+        if out is None:
+            out = torch.empty(M, N, device=x.device, dtype=x.dtype)
+        return _w8_epilogue_cpu(_w4_matmul_cpu(x, q4, scale), x, bias, act, residual, out)
+    if M <= W8_SKINNY_MAX_M:
+        return linear_skinny_w4(x, q4, scale, bias, act, residual, out)
+    if scratch is None:
+        scratch = torch.empty(N * K, device=x.device, dtype=torch.bfloat16)
+    if scratch.dtype != torch.bfloat16 or scratch.numel() < N * K or not scratch.is_contiguous():
+        raise ValueError(f"linear_w4: scratch must be contiguous bf16 with at least {N * K} elements")
+    w = dequant_w4(q4, scale, scratch.view(-1)[: N * K].view(N, K))
     return linear(x, w, bias, act=act, residual=residual, out=out)[0]
 
 

@@ -27,6 +27,8 @@ the acceptance rate goes to stderr.
 
 ``--weights int8`` quantises the block matrices and the LM head per output row while loading
 (int8 weight-only inference; the draft of ``--draft-checkpoint`` follows ``--draft-weights``).
+``--weights int4g128`` stores them as 4-bit values with one scale per 128-element group of K
+instead (every such matrix needs K % 128 == 0).
 """
 from __future__ import annotations
 
@@ -57,9 +59,11 @@ def main(argv=None) -> int:
                     "draft model (same vocabulary; greedy only)")
     ap.add_argument("--lookahead", type=int, default=4, help="tokens the draft proposes per round")
     ap.add_argument("--device", choices=("cpu", "cuda"), default=None, help="default: cuda when available")
-    ap.add_argument("--weights", choices=("bf16", "int8"), default="bf16", help="int8: weight-only quantisation of "
-                    "the block matrices and the LM head at load")
-    ap.add_argument("--draft-weights", choices=("bf16", "int8"), default="bf16", help="the same for the draft model")
+    ap.add_argument("--weights", choices=("bf16", "int8", "int4g128"), default="bf16",
+                    help="int8 / int4g128: weight-only quantisation of the block matrices and the LM head at load "
+                    "(per output row / 4-bit with one scale per 128 k)")
+    ap.add_argument("--draft-weights", choices=("bf16", "int8", "int4g128"), default="bf16",
+                    help="the same for the draft model")
     a = ap.parse_args(argv)
 
     import torch

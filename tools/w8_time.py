@@ -1,7 +1,8 @@
-"""Time of the skinny-M kernel (int8 and bf16 weights) against ``ops.linear`` per GEMM shape,
-and end-to-end tokens/s of bf16, bf16 ``skinny=True`` and int8 generators, on one GPU.
+"""Time of the skinny-M kernel (int8, int4g128 and bf16 weights) against ``ops.linear`` per GEMM
+shape, and end-to-end tokens/s of bf16, bf16 ``skinny=True``, int8 and int4g128 generators, on
+one GPU.
 
-    python tools/w8_time.py                       # both tables (profiles/r12_w8_decode.md)
+    python tools/w8_time.py                       # both tables (profiles/r12_w8_decode.md, r13_w4_decode.md)
     python tools/w8_time.py --parts gemm --models llama3-1b --rows 1,16
     python tools/w8_time.py --parts e2e --batches 1 --speculative
 
@@ -15,13 +16,16 @@ events.  Each call takes the next of several copies of the weight (together at l
 ``--cold-mb``, 512 MB by default, capped at 64 copies) so the matrix comes from HBM rather
 than from the 256 MB Infinity Cache, as it does inside a decode step of a model that does not
 fit there; ``copies`` is printed.  Variants: ``w8`` = ops.linear_w8 (the skinny kernel up to
-W8_SKINNY_MAX_M rows, dequantise + ops.linear above), ``skinny_bf16`` (up to 16 rows),
+W8_SKINNY_MAX_M rows, dequantise + ops.linear above), ``w4`` = ops.linear_w4 on the int4g128
+format of the same weights (the same routes), ``skinny_bf16`` (up to 16 rows),
 ``linear`` = ops.linear on bf16 weights, ``dequant_linear`` = dequant_w8 + ops.linear at every
-M (the crossover).  GB/s counts the weight bytes of the variant's own format once per call.
+M (the crossover).  GB/s counts the weight bytes of the variant's own format once per call
+(for ``w4`` the packed nibbles and their group scales: N K / 2 + N K / 32 bytes).
 
 End to end (``--parts e2e``): greedy ``generate_batch`` (eager step) of one set of weights as
-a bf16 generator, the same with ``skinny=True`` and quantised to int8; ``--speculative`` adds
-``generate_speculative`` of the bf16 target with its own int8 generator as the draft.  A
+a bf16 generator, the same with ``skinny=True`` and quantised to int8 and to int4g128;
+``--speculative`` adds ``generate_speculative`` of the bf16 target with its own int8 and
+int4g128 generators as the draft.  A
 window is one whole call (prefill + new tokens); tok/s = B * new_tokens / median.
 Prints one JSON line per shape, then both tables in markdown."""
 from __future__ import annotations
@@ -86,12 +90,14 @@ def gemm_part(a, dev):
             copies = max(2, min(64, -(-a.cold_mb * (1 << 20) // (N * K))))
             w = [torch.randn(N, K, device=dev, dtype=torch.bfloat16) * (K ** -0.5) for _ in range(copies)]
             qs = [ops.quantize_w8(t) for t in w]
+            q4s = [ops.quantize_w4(t) for t in w]
             scratch = torch.empty(N * K, device=dev, dtype=torch.bfloat16)
             for M in (int(m) for m in a.rows.split(",")):
                 x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
                 y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
                 variants = {
                     "w8": lambda i: ops.linear_w8(x, *qs[i % copies], out=y, scratch=scratch),
+                    "w4": lambda i: ops.linear_w4(x, *q4s[i % copies], out=y, scratch=scratch),
                     "linear": lambda i: ops.linear(x, w[i % copies], out=y),
                     "dequant_linear": lambda i: ops.linear(
                         x, ops.dequant_w8(*qs[i % copies], scratch.view(N, K)), out=y),
@@ -102,12 +108,13 @@ def gemm_part(a, dev):
                 rec = {"model": mname, "layer": lname, "N": N, "K": K, "M": M, "copies": copies,
                        "w8_route": "skinny" if M <= ops.W8_SKINNY_MAX_M else "dequant"}
                 for name, sec in t.items():
-                    wbytes = N * K * (1 if name in ("w8", "dequant_linear") else 2)
+                    wbytes = N * K // 2 + N * K // 32 if name == "w4" else \
+                        N * K * (1 if name in ("w8", "dequant_linear") else 2)
                     rec[f"{name}_us"] = round(sec * 1e6, 1)
                     rec[f"{name}_gbs"] = round(wbytes / sec * 1e-9)
                 print(json.dumps(rec), flush=True)
                 recs.append(rec)
-            del w, qs, scratch
+            del w, qs, q4s, scratch
             torch.cuda.empty_cache()
     return recs
 
@@ -119,13 +126,16 @@ def e2e_part(a, dev):
         cfg = _config(mname)
         base = mipipe.Generator(cfg, dev, dtype=torch.bfloat16, seed=0)
         gens = {"bf16": base, "bf16_skinny": mipipe.Generator.from_model(base.model, skinny=True),
-                "int8": mipipe.Generator.from_model(base.model, weights="int8")}
+                "int8": mipipe.Generator.from_model(base.model, weights="int8"),
+                "int4g128": mipipe.Generator.from_model(base.model, weights="int4g128")}
         for B in (int(b) for b in a.batches.split(",")):
             prompt = torch.randint(0, cfg.vocab_size, (B, S0), generator=torch.Generator().manual_seed(B))
             rows = list(prompt)
             variants = {n: (lambda g=g: g.generate_batch(rows, N, graphs=False)[0]) for n, g in gens.items()}
             if a.speculative:
                 variants["bf16_spec_int8_draft"] = lambda: base.generate_speculative(rows, N, gens["int8"], lookahead=4)
+                variants["bf16_spec_int4g128_draft"] = lambda: base.generate_speculative(rows, N, gens["int4g128"],
+                                                                                         lookahead=4)
             outs = {n: fn() for n, fn in variants.items()}                  # warm
             torch.cuda.synchronize()
             times = {n: [] for n in variants}
@@ -141,11 +151,15 @@ def e2e_part(a, dev):
                 rec[f"{n}_tok_s"] = round(B * N / statistics.median(times[n]), 1)
             rec["skinny_vs_bf16"] = round(rec["bf16_skinny_tok_s"] / rec["bf16_tok_s"], 3)
             rec["int8_vs_bf16"] = round(rec["int8_tok_s"] / rec["bf16_tok_s"], 3)
+            rec["int4g128_vs_bf16"] = round(rec["int4g128_tok_s"] / rec["bf16_tok_s"], 3)
+            rec["int4g128_vs_int8"] = round(rec["int4g128_tok_s"] / rec["int8_tok_s"], 3)
             rec["skinny_tokens_equal_bf16"] = bool(torch.equal(outs["bf16"], outs["bf16_skinny"]))
             if a.speculative:
                 st = outs["bf16_spec_int8_draft"][2]
                 rec["spec_accept_rate"] = round(st["accepted"] / max(1, st["drafted"]), 3)
                 rec["spec_equals_bf16"] = bool(torch.equal(outs["bf16_spec_int8_draft"][0], outs["bf16"]))
+                st = outs["bf16_spec_int4g128_draft"][2]
+                rec["spec4_accept_rate"] = round(st["accepted"] / max(1, st["drafted"]), 3)
             print(json.dumps(rec), flush=True)
             recs.append(rec)
         del base, gens
@@ -155,11 +169,13 @@ def e2e_part(a, dev):
 
 def _markdown(gemm, e2e):
     if gemm:
-        print("\n| model | layer | N x K | M | w8 us | w8 GB/s | skinny bf16 us | GB/s | linear us | GB/s | dequant+linear us |")
-        print("|---|---|---|---|---|---|---|---|---|---|---|")
+        print("\n| model | layer | N x K | M | w4 us | w4 GB/s | w8 us | w8 GB/s | skinny bf16 us | GB/s | linear us | GB/s "
+              "| dequant+linear us |")
+        print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
         for r in gemm:
             sk = (r.get("skinny_bf16_us", "-"), r.get("skinny_bf16_gbs", "-"))
-            print(f"| {r['model']} | {r['layer']} | {r['N']} x {r['K']} | {r['M']} | {r['w8_us']} ({r['w8_route']}) | "
+            print(f"| {r['model']} | {r['layer']} | {r['N']} x {r['K']} | {r['M']} | {r['w4_us']} | {r['w4_gbs']} | "
+                  f"{r['w8_us']} ({r['w8_route']}) | "
                   f"{r['w8_gbs']} | {sk[0]} | {sk[1]} | {r['linear_us']} | {r['linear_gbs']} | {r['dequant_linear_us']} |")
     if e2e:
         keys = [k for k in e2e[0] if k not in ("model", "B", "prompt", "new_tokens")]
