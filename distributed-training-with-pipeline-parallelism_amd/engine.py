@@ -589,7 +589,7 @@ class PipelineTrainer:
         # stream-K kernels synchronise their workgroups and assume all of them resident; a
         # second lane's kernels holding CUs left a Llama-3 1B step hung in that mode
         # (profiles/r3_model_families_1gpu.txt)
-        from .ops.kernels import GEMM_BACKEND
+        from .ops.gemm import GEMM_BACKEND
         my_layers = sum(layer_ranges[st][1] - layer_ranges[st][0] for st in my_stages)
         params_est = (cfg.layer_params() * my_layers + (cfg.vocab_padded * cfg.d_model if 0 in my_stages else 0)
                       + (cfg.vocab_padded * cfg.d_model if self.split_head else 0))

@@ -35,7 +35,8 @@ csrc/kernels/gemv_skinny.hip (:func:`ops.linear_w8`); ``skinny=True`` runs bf16 
 through the same kernel.  ``weights="int4g128"`` holds the same matrices as packed 4-bit
 values with one f32 scale per 128-element group of K (:func:`ops.quantize_w4`,
 :func:`ops.linear_w4`): half the streamed bytes again.  Every mode above works on every kind
-of generator.
+of generator.  The formats are the entries of ``ops.QUANT_FORMATS`` (ops/quant.py); this module
+reaches them only by name, through that table and :func:`ops.linear_q`.
 """
 from __future__ import annotations
 
@@ -108,7 +109,7 @@ class KVCache:
 
 
 QUANTIZED = ("attn.wqkv.weight", "attn.wo.weight", "ffn.w1.weight", "ffn.w2.weight", "ffn.w13.weight")
-QUANT_FORMATS = ("int8", "int4g128")
+QUANT_FORMATS = tuple(ops.QUANT_FORMATS)
 
 
 def model_param_specs(cfg: NativeConfig) -> List[ParamSpec]:
@@ -158,12 +159,11 @@ class QuantWeights:
         self.q: Dict[str, torch.Tensor] = {}
         self.scale: Dict[str, torch.Tensor] = {}
         self.dense: Dict[str, torch.Tensor] = {}
-        if fmt == "int4g128":
-            bad = [(n, self.specs[n].shape) for n in self.order
-                   if self.quantized(n) and self.specs[n].shape[1] % ops.W4_GROUP != 0]
-            if bad:
-                raise ValueError(f"QuantWeights: int4g128 needs K % {ops.W4_GROUP} == 0 in every quantised matrix; "
-                                 f"{bad[0][0]} is {tuple(bad[0][1])}")
+        mult = ops.QUANT_FORMATS[fmt].k_format
+        bad = [(n, self.specs[n].shape) for n in self.order if self.quantized(n) and self.specs[n].shape[1] % mult != 0]
+        if bad:
+            raise ValueError(f"QuantWeights: {fmt} needs K % {mult} == 0 in every quantised matrix; "
+                             f"{bad[0][0]} is {tuple(bad[0][1])}")
 
     def quantized(self, name: str) -> bool:
         return name == self.head_name or name.endswith(QUANTIZED)
@@ -183,7 +183,7 @@ class QuantWeights:
         s = self.specs[name]
         t = t.detach().float().reshape(s.shape)
         if self.quantized(name):
-            q, scale = ops.quantize_w4(t) if self.fmt == "int4g128" else ops.quantize_w8(t)
+            q, scale = ops.QUANT_FORMATS[self.fmt].quantize(t)
             self.q[name], self.scale[name] = q.to(self.device), scale.to(self.device)
         # dense: everything but the block matrices and an untied head (a tied head is also
         # the embedding table, which stays dense)
@@ -212,9 +212,7 @@ class QuantWeights:
             self.put(n, sd[n])
 
     def _what(self, n: str) -> torch.Tensor:
-        if self.fmt == "int4g128":
-            return ops.dequant_w4(self.q[n].cpu(), self.scale[n].cpu())
-        return (self.q[n].float() * self.scale[n][:, None]).cpu()
+        return ops.QUANT_FORMATS[self.fmt].dequant(self.q[n].cpu(), self.scale[n].cpu())
 
     def effective_state_dict(self) -> Dict[str, torch.Tensor]:
         """f32 CPU tensors by FQN of the weights this generator computes with: ``q * scale``
@@ -369,16 +367,15 @@ class Generator:
         if self.weights != "bf16":
             key = A.head_name if wname == "lm_head" else wname
             q, scale = A.q[key], A.scale[key]
-            w4 = self.weights == "int4g128"
-            scratch = None
-            if x.is_cuda and (x.shape[0] > ops.W8_SKINNY_MAX_M or (not w4 and q.shape[1] % 32 != 0)):
+            scratch, kmult = None, ops.QUANT_FORMATS[self.weights].k_skinny
+            if x.is_cuda and (x.shape[0] > ops.W8_SKINNY_MAX_M or x.shape[1] % kmult != 0):
                 if self._scratch is None:
                     if torch.cuda.is_current_stream_capturing():
                         raise RuntimeError("Generator: the dequantisation scratch cannot be allocated inside a graph "
                                            "capture (run one step eagerly first)")
                     self._scratch = torch.empty(A.max_matrix_numel(), device=self.device, dtype=torch.bfloat16)
                 scratch = self._scratch
-            return (ops.linear_w4 if w4 else ops.linear_w8)(x, q, scale, bias, act, residual, out, scratch=scratch)
+            return ops.linear_q(x, q, scale, self.weights, bias, act, residual, out, scratch=scratch)
         w = self.model.head_weight() if wname == "lm_head" else A.w(wname)
         if self.skinny and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[0] <= ops.SKINNY_MAX_M \
                 and w.shape[1] % 32 == 0 and act in ("none", "gelu", "gelu_tanh"):

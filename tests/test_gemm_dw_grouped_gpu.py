@@ -219,8 +219,8 @@ def test_run_wjobs_long_token_group(monkeypatch, group3):
     the grouped 256x256 engine, and with it switched off (MIPIPE_WGRAD_GROUP3=0's behaviour).
     Both stay inside the bound of the float64 reference; the bias sum lands in its own vector."""
     K = ops.kernels
-    monkeypatch.setattr(K, "_GROUP3_MIN_T", 256)
-    monkeypatch.setattr(K, "_WGRAD_GROUP3", group3)
+    monkeypatch.setattr(ops.wgrad, "_GROUP3_MIN_T", 256)      # the module that owns the switches
+    monkeypatch.setattr(ops.wgrad, "_WGRAD_GROUP3", group3)
     rep = R.Report(f"dwgroup-wrapper-{int(group3)}")
     T = 320
     g = torch.Generator().manual_seed(5)

@@ -3,7 +3,9 @@ the grouped launches (short-token 64x64 engine, long-token 256x256 split-K engin
 deferred list that spans layers and token counts is cut into chunks, and that the result of the
 whole list equals running every job alone.  The two grouped launchers and the per-job GEMM are
 replaced by float32 CPU arithmetic that records what it was given; ``_gpu`` answers yes, so the
-planner sees the tensors as it would on the GPU."""
+planner sees the tensors as it would on the GPU.  Every stand-in is installed in the module that
+owns the name (``ops.wgrad`` looks the foreign ones up there when it runs); ``rec`` and the plans
+show that the stand-ins are what ran."""
 import pytest
 import torch
 
@@ -11,6 +13,7 @@ import mipipe  # noqa: F401
 from mipipe import ops
 
 K = ops.kernels
+W, G = ops.wgrad, ops.gemm
 BF16, F32 = torch.bfloat16, torch.float32
 
 
@@ -22,11 +25,11 @@ def _cpu_dw(dy, x, dw, alpha=1.0):
 @pytest.fixture
 def rec(monkeypatch):
     log = dict(small=[], long=[], single=[])
-    monkeypatch.setattr(K, "_gpu", lambda t: True)
-    monkeypatch.setattr(K, "_WGRAD_GROUP", True)
-    monkeypatch.setattr(K, "_WGRAD_GROUP3", True)
-    monkeypatch.setattr(K, "GEMM_BACKEND", "hip")
-    monkeypatch.setattr(K, "_GROUP3_MIN_T", 8192)
+    monkeypatch.setattr(ops._base, "_gpu", lambda t: True)
+    monkeypatch.setattr(W, "_WGRAD_GROUP", True)
+    monkeypatch.setattr(W, "_WGRAD_GROUP3", True)
+    monkeypatch.setattr(G, "GEMM_BACKEND", "hip")
+    monkeypatch.setattr(W, "_GROUP3_MIN_T", 8192)
 
     def group(kind):
         def run(part):
@@ -43,10 +46,10 @@ def rec(monkeypatch):
         log["single"].append((dy, x, dw))
         return _cpu_dw(dy, x, dw, alpha)
 
-    monkeypatch.setattr(K, "_run_group_small", group("small"))
-    monkeypatch.setattr(K, "_run_group_long", group("long"))
-    monkeypatch.setattr(K, "linear_dw", single)
-    monkeypatch.setattr(K, "colsum", lambda x, db: db.add_(x.float().sum(0)))
+    monkeypatch.setattr(W, "_run_group_small", group("small"))
+    monkeypatch.setattr(W, "_run_group_long", group("long"))
+    monkeypatch.setattr(G, "linear_dw", single)
+    monkeypatch.setattr(ops.elementwise_optim, "colsum", lambda x, db: db.add_(x.float().sum(0)))
     return log
 
 
@@ -108,14 +111,14 @@ def test_plan_and_results(rec):
 
 def test_switches(rec, monkeypatch):
     jobs, kinds, _ = _jobs()
-    monkeypatch.setattr(K, "_WGRAD_GROUP3", False)
+    monkeypatch.setattr(W, "_WGRAD_GROUP3", False)
     small, long_, rest = K.plan_wjobs(jobs)
     assert not long_ and [len(p) for p in small] == [3]
     assert len(rest) == len(jobs) - 3
-    monkeypatch.setattr(K, "_WGRAD_GROUP", False)
+    monkeypatch.setattr(W, "_WGRAD_GROUP", False)
     assert K.plan_wjobs(jobs) == ([], [], jobs)
-    monkeypatch.setattr(K, "_WGRAD_GROUP", True)
-    monkeypatch.setattr(K, "GEMM_BACKEND", "blas")
+    monkeypatch.setattr(W, "_WGRAD_GROUP", True)
+    monkeypatch.setattr(G, "GEMM_BACKEND", "blas")
     assert K.plan_wjobs(jobs) == ([], [], jobs)
 
 
