@@ -6,21 +6,39 @@
 namespace mipipe_bind {
 namespace {
 
+// bytes of one int8 cache row (attention_kv8.hip): payload, Hkv f32 scales, padding to 16
+int64_t kv8_row_bytes(int64_t Hkv, int64_t D) { return (Hkv * D + 4 * Hkv + 15) / 16 * 16; }
+
 // The KV-cache geometry every kernel here indexes: k_cache / v_cache are [B, Smax, Hkv*D] views
 // with a unit inner stride and 16-byte aligned base, batch and token strides.  `q_aligned`: the
 // same of the caller's query rows (`qname`), a conjunct of the one alignment message; `d`: the
-// head dim's name in the caller's messages.  Returns Smax.
+// head dim's name in the caller's messages.  `kv8`: the caches are int8 rows of
+// kv8_row_bytes(Hkv, D) bytes (attention_kv8.hip) instead.  Returns Smax.
 int64_t kv_cache_args(const char* fn, const char* qname, bool q_aligned, const char* d, const torch::Tensor& k_cache,
-                      const torch::Tensor& v_cache, int64_t B, int64_t Hkv, int64_t D) {
+                      const torch::Tensor& v_cache, int64_t B, int64_t Hkv, int64_t D, bool kv8 = false) {
   TORCH_CHECK(k_cache.dim() == 3 && v_cache.dim() == 3 && k_cache.stride(2) == 1 && v_cache.stride(2) == 1, fn,
               ": caches are [B, Smax, Hkv*", d, "] with a unit inner stride");
   const int64_t Smax = k_cache.size(1);
-  TORCH_CHECK(k_cache.size(0) == B && v_cache.size(0) == B && v_cache.size(1) == Smax && k_cache.size(2) == Hkv * D &&
-                  v_cache.size(2) == Hkv * D, fn, ": cache shape");
-  TORCH_CHECK(q_aligned && aligned16(k_cache) && aligned16(v_cache) && k_cache.stride(0) % 8 == 0 &&
-                  k_cache.stride(1) % 8 == 0 && v_cache.stride(0) % 8 == 0 && v_cache.stride(1) % 8 == 0,
+  const int64_t width = kv8 ? kv8_row_bytes(Hkv, D) : Hkv * D, per = kv8 ? 16 : 8;     // elements per 16 bytes
+  TORCH_CHECK(k_cache.size(0) == B && v_cache.size(0) == B && v_cache.size(1) == Smax && k_cache.size(2) == width &&
+                  v_cache.size(2) == width, fn, kv8 ? ": cache shape (int8 rows are round_up(Hkv*D + 4*Hkv, 16) bytes)"
+                                                    : ": cache shape");
+  TORCH_CHECK(q_aligned && aligned16(k_cache) && aligned16(v_cache) && k_cache.stride(0) % per == 0 &&
+                  k_cache.stride(1) % per == 0 && v_cache.stride(0) % per == 0 && v_cache.stride(1) % per == 0,
               fn, ": ", qname, " / cache rows must be 16-byte aligned");
+  // the int8 kernels index the rows of one sequence with 32-bit byte offsets
+  TORCH_CHECK(!kv8 || (Smax * k_cache.stride(1) <= (int64_t)UINT32_MAX && Smax * v_cache.stride(1) <= (int64_t)UINT32_MAX),
+              fn, ": one sequence of an int8 cache must stay below 4 GiB");
   return Smax;
+}
+
+// the caches of an attention call: both bf16, or both int8 (the kv8 format); true for int8
+bool kv_cache_is_kv8(const char* fn, const torch::Tensor& k_cache, const torch::Tensor& v_cache) {
+  for (const torch::Tensor* t : {&k_cache, &v_cache})
+    TORCH_CHECK(t->is_cuda() && (t->scalar_type() == torch::kBFloat16 || t->scalar_type() == torch::kChar), fn,
+                ": q/k_cache/v_cache/o must be bf16 GPU tensors (or both caches int8)");
+  TORCH_CHECK(k_cache.scalar_type() == v_cache.scalar_type(), fn, ": k_cache and v_cache must share a dtype");
+  return k_cache.scalar_type() == torch::kChar;
 }
 
 // Decode attention (attention_decode.hip): one query row per sequence against its KV cache.
@@ -31,8 +49,9 @@ int64_t attn_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cach
                     torch::Tensor o, int64_t H, int64_t Hkv, int64_t D, int64_t max_len, double scale,
                     int64_t splits) {
   req(lens, torch::kInt32, "lens");
-  for (const torch::Tensor* t : {&q, &k_cache, &v_cache, &o})
+  for (const torch::Tensor* t : {&q, &o})
     TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16, "attn_decode: q/k_cache/v_cache/o must be bf16 GPU tensors");
+  const bool kv8 = kv_cache_is_kv8("attn_decode", k_cache, v_cache);
   TORCH_CHECK(q.dim() == 2 && o.dim() == 2 && q.stride(1) == 1 && o.stride(1) == 1, "attn_decode: q/o are [B, H*D] rows");
   TORCH_CHECK(D == 64 || D == 128, "attn_decode: head_dim ", D, " is not supported (64 or 128)");
   TORCH_CHECK(Hkv >= 1 && H >= 1 && H % Hkv == 0 && H / Hkv <= 8,
@@ -40,7 +59,7 @@ int64_t attn_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cach
   const int64_t B = q.size(0);
   TORCH_CHECK(q.size(1) == H * D && o.size(0) == B && o.size(1) == H * D, "attn_decode: q/o shape");
   const int64_t Smax =
-      kv_cache_args("attn_decode", "q", aligned16(q) && q.stride(0) % 8 == 0, "D", k_cache, v_cache, B, Hkv, D);
+      kv_cache_args("attn_decode", "q", aligned16(q) && q.stride(0) % 8 == 0, "D", k_cache, v_cache, B, Hkv, D, kv8);
   TORCH_CHECK(lens.numel() == B, "attn_decode: lens must hold one length per sequence");
   TORCH_CHECK(max_len >= 1 && max_len <= Smax, "attn_decode: max_len ", max_len, " outside [1, ", Smax, "]");
   TORCH_CHECK(splits >= 0 && splits <= max_len && splits <= 256, "attn_decode: splits ", splits,
@@ -50,10 +69,12 @@ int64_t attn_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cach
   // per-split partial outputs + (max, sum): from the caching allocator on the current stream
   torch::Tensor ws = torch::empty({mp_attn_decode_ws_floats((int)B, (int)H, (int)D, ns)},
                                   q.options().dtype(torch::kFloat32));
-  check(mp_attn_decode(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), lens.data_ptr<int>(), o.data_ptr(),
-                       ws.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)D, (int)Smax, (int)max_len, q.stride(0),
-                       k_cache.stride(0), k_cache.stride(1), v_cache.stride(0), v_cache.stride(1), o.stride(0),
-                       (float)scale, ns, cur_stream()),
+  // int8 caches: the same arguments (strides of an int8 tensor are bytes) to the kv8 kernel
+  check((kv8 ? mp_attn_decode_kv8 : mp_attn_decode)(
+            q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), lens.data_ptr<int>(), o.data_ptr(),
+            ws.data_ptr<float>(), (int)B, (int)H, (int)Hkv, (int)D, (int)Smax, (int)max_len, q.stride(0),
+            k_cache.stride(0), k_cache.stride(1), v_cache.stride(0), v_cache.stride(1), o.stride(0), (float)scale, ns,
+            cur_stream()),
         "attn_decode");
   return ns;
 }
@@ -68,8 +89,9 @@ int64_t attn_append(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cach
                     int64_t max_len, double scale, int64_t splits) {
   req(base, torch::kInt32, "base");
   if (counts.has_value()) req(*counts, torch::kInt32, "counts");
-  for (const torch::Tensor* t : {&q, &k_cache, &v_cache, &o})
+  for (const torch::Tensor* t : {&q, &o})
     TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16, "attn_append: q/k_cache/v_cache/o must be bf16 GPU tensors");
+  const bool kv8 = kv_cache_is_kv8("attn_append", k_cache, v_cache);
   TORCH_CHECK(q.dim() == 2 && o.dim() == 2 && q.stride(1) == 1 && o.stride(1) == 1, "attn_append: q/o are [B*T, H*D] rows");
   TORCH_CHECK(D == 64 || D == 128, "attn_append: head_dim ", D, " is not supported (64 or 128)");
   TORCH_CHECK(Hkv >= 1 && H >= 1 && H % Hkv == 0 && H / Hkv <= 8,
@@ -77,7 +99,7 @@ int64_t attn_append(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cach
   // the batch is the cache's here: q / o hold B * T rows
   const int64_t B = k_cache.dim() == 3 ? k_cache.size(0) : 0;
   const int64_t Smax =
-      kv_cache_args("attn_append", "q", aligned16(q) && q.stride(0) % 8 == 0, "D", k_cache, v_cache, B, Hkv, D);
+      kv_cache_args("attn_append", "q", aligned16(q) && q.stride(0) % 8 == 0, "D", k_cache, v_cache, B, Hkv, D, kv8);
   TORCH_CHECK(T >= 1 && B >= 1 && B * T <= INT_MAX && q.size(0) == B * T && o.size(0) == B * T,
               "attn_append: q/o must hold B * T = ", B * T, " rows");
   TORCH_CHECK(q.size(1) == H * D && o.size(1) == H * D, "attn_append: q/o shape");
@@ -96,11 +118,11 @@ int64_t attn_append(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cach
   const int ns = splits > 0 ? (int)splits : mp_attn_append_plan((int)B, (int)T, (int)Hkv, (int)rep, (int)max_len);
   torch::Tensor ws = torch::empty({mp_attn_append_ws_floats((int)B, (int)T, (int)H, (int)D, ns)},
                                   q.options().dtype(torch::kFloat32));
-  check(mp_attn_append(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), base.data_ptr<int>(),
-                       counts.has_value() ? counts->data_ptr<int>() : nullptr, o.data_ptr(), ws.data_ptr<float>(),
-                       (int)B, (int)T, (int)H, (int)Hkv, (int)D, (int)Smax, (int)max_len, q.stride(0),
-                       k_cache.stride(0), k_cache.stride(1), v_cache.stride(0), v_cache.stride(1), o.stride(0),
-                       (float)scale, ns, cur_stream()),
+  check((kv8 ? mp_attn_append_kv8 : mp_attn_append)(
+            q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), base.data_ptr<int>(),
+            counts.has_value() ? counts->data_ptr<int>() : nullptr, o.data_ptr(), ws.data_ptr<float>(), (int)B, (int)T,
+            (int)H, (int)Hkv, (int)D, (int)Smax, (int)max_len, q.stride(0), k_cache.stride(0), k_cache.stride(1),
+            v_cache.stride(0), v_cache.stride(1), o.stride(0), (float)scale, ns, cur_stream()),
         "attn_append");
   return ns;
 }
@@ -153,10 +175,12 @@ void rope_kv_append(torch::Tensor qkv, c10::optional<torch::Tensor> cs, c10::opt
   const char* fn = "rope_kv_append";
   TORCH_CHECK(Dh == 64 || Dh == 128, fn, ": head_dim ", Dh, " is not supported (64 or 128)");
   TORCH_CHECK(H >= 1 && Hkv >= 1 && H <= 65535 && Hkv <= 65535, fn, ": bad head counts");
+  // int8 caches (both): the quantising append of attention_kv8.hip
+  const bool kv8 = k_cache.scalar_type() == torch::kChar && v_cache.scalar_type() == torch::kChar;
   for (const torch::Tensor* t : {&qkv, &k_cache, &v_cache}) {
     TORCH_CHECK(t->is_cuda() && t->get_device() == qkv.get_device(), fn, ": qkv / k_cache / v_cache must be on one GPU");
-    TORCH_CHECK(t->scalar_type() == torch::kBFloat16, fn, ": qkv / k_cache / v_cache must be bf16, got ",
-                t->scalar_type());
+    TORCH_CHECK(t->scalar_type() == torch::kBFloat16 || (kv8 && t != &qkv), fn,
+                ": qkv / k_cache / v_cache must be bf16 (or both caches int8), got ", t->scalar_type());
   }
   const int64_t width = (H + 2 * Hkv) * Dh;
   TORCH_CHECK(qkv.dim() == 2 && qkv.size(1) == width && qkv.stride(1) == 1, fn, ": qkv must be [B, (H + 2 Hkv) Dh] rows");
@@ -164,11 +188,12 @@ void rope_kv_append(torch::Tensor qkv, c10::optional<torch::Tensor> cs, c10::opt
   const int64_t B = qkv.size(0) / T, rows = qkv.size(0);
   TORCH_CHECK(B >= 1 && B <= 65535, fn, ": batch outside [1, 65535]");
   const int64_t Smax = kv_cache_args(fn, "qkv", aligned16(qkv) && (rows == 1 || qkv.stride(0) % 8 == 0), "Dh", k_cache,
-                                     v_cache, B, Hkv, Dh);
+                                     v_cache, B, Hkv, Dh, kv8);
   TORCH_CHECK(Smax >= 1 && Smax <= INT_MAX, fn, ": cache shape");
   // the kernel writes qkv and both caches: no two rows of one may overlap
   TORCH_CHECK(rows == 1 || qkv.stride(0) >= width, fn, ": qkv rows overlap");
-  TORCH_CHECK(k_cache.stride(1) >= Hkv * Dh && v_cache.stride(1) >= Hkv * Dh &&
+  const int64_t row_elems = kv8 ? kv8_row_bytes(Hkv, Dh) : Hkv * Dh;
+  TORCH_CHECK(k_cache.stride(1) >= row_elems && v_cache.stride(1) >= row_elems &&
                   (B == 1 || (k_cache.stride(0) >= Smax * k_cache.stride(1) && v_cache.stride(0) >= Smax * v_cache.stride(1))),
               fn, ": cache rows overlap");
   gen_vec(fn, "pos", pos, torch::kInt32, B, qkv);
@@ -187,11 +212,14 @@ void rope_kv_append(torch::Tensor qkv, c10::optional<torch::Tensor> cs, c10::opt
     cp = cs->data_ptr<float>();
     sp = sn->data_ptr<float>();
   }
-  check(mp_rope_kv_append(qkv.data_ptr(), cp, sp, k_cache.data_ptr(), v_cache.data_ptr(), pos.data_ptr<int>(),
-                          active.has_value() ? active->data_ptr<uint8_t>() : nullptr,
-                          counts.has_value() ? counts->data_ptr<int>() : nullptr, (int)B, (int)T, (int)H, (int)Hkv,
-                          (int)Dh, (int)Smax, qkv.stride(0), k_cache.stride(0), k_cache.stride(1), v_cache.stride(0),
-                          v_cache.stride(1), rope ? 1 : 0, cur_stream()),
+  // qkv's row stride as the kernels index it (a single row may have any)
+  const int64_t qkv_ld = rows == 1 ? width : qkv.stride(0);
+  check((kv8 ? mp_rope_kv_append_kv8 : mp_rope_kv_append)(
+            qkv.data_ptr(), cp, sp, k_cache.data_ptr(), v_cache.data_ptr(), pos.data_ptr<int>(),
+            active.has_value() ? active->data_ptr<uint8_t>() : nullptr,
+            counts.has_value() ? counts->data_ptr<int>() : nullptr, (int)B, (int)T, (int)H, (int)Hkv, (int)Dh,
+            (int)Smax, kv8 ? qkv_ld : qkv.stride(0), k_cache.stride(0), k_cache.stride(1), v_cache.stride(0),
+            v_cache.stride(1), rope ? 1 : 0, cur_stream()),
         fn);
 }
 

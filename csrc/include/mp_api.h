@@ -127,6 +127,21 @@ int mp_attn_append(const void* q, const void* k, const void* v, const int* base,
                    int64_t k_ts, int64_t v_bs, int64_t v_ts, int64_t o_stride, float scale, int splits, hipStream_t st);
 int mp_attn_append_plan(int B, int T, int Hkv, int rep, int max_len);
 int64_t mp_attn_append_ws_floats(int B, int T, int H, int D, int splits);
+// ---- attention_kv8.hip.  The int8 KV cache: a row of Hkv heads of dim D is
+// round_up(Hkv * D + 4 * Hkv, 16) bytes (int8 payload, Hkv f32 scales, zero padding).  The
+// arguments of the three launchers above that they stand in for, with the caches' batch / token
+// strides in bytes; planners and workspaces are those of the bf16 kernels.
+int mp_attn_decode_kv8(const void* q, const void* k, const void* v, const int* lens, void* o, float* ws, int B, int H,
+                       int Hkv, int D, int Smax, int max_len, int64_t q_stride, int64_t k_bs, int64_t k_ts,
+                       int64_t v_bs, int64_t v_ts, int64_t o_stride, float scale, int splits, hipStream_t st);
+int mp_attn_append_kv8(const void* q, const void* k, const void* v, const int* base, const int* counts, void* o,
+                       float* ws, int B, int T, int H, int Hkv, int D, int Smax, int max_len, int64_t q_stride,
+                       int64_t k_bs, int64_t k_ts, int64_t v_bs, int64_t v_ts, int64_t o_stride, float scale,
+                       int splits, hipStream_t st);
+int mp_rope_kv_append_kv8(void* qkv, const float* cs, const float* sn, void* kc, void* vc, const int* pos,
+                          const uint8_t* active, const int* counts, int B, int T, int H, int Hkv, int Dh, int Smax,
+                          int64_t qkv_ld, int64_t k_bs, int64_t k_ts, int64_t v_bs, int64_t v_ts, int rope,
+                          hipStream_t st);
 // ---- generate.hip
 int mp_embed_pos(const int64_t* idx, const int* pos, const void* wte, const void* wpe, void* out, int B, int D,
                  int n_tok, int n_pos, int f32, hipStream_t st);

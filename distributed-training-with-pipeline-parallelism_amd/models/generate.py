@@ -37,6 +37,15 @@ values with one f32 scale per 128-element group of K (:func:`ops.quantize_w4`,
 :func:`ops.linear_w4`): half the streamed bytes again.  Every mode above works on every kind
 of generator.  The formats are the entries of ``ops.QUANT_FORMATS`` (ops/quant.py); this module
 reaches them only by name, through that table and :func:`ops.linear_q`.
+
+int8 KV cache (``Generator(..., kv_cache="int8")``, ``KVCache(..., kv="int8")``): every K / V
+row is stored as int8 with one f32 scale per (token, KV head) inside the row
+(:func:`ops.generate.kv_quantize`; csrc/kernels/attention_kv8.hip), 0.52-0.53x the bytes of
+bf16.  Every writer goes through the quantising :func:`ops.rope_kv_append`, the attention ops
+read the rows as stored.  Independent of ``weights=`` and ``skinny=``.  A prefill attends to its
+own exact K / V and stores them quantised; :meth:`Generator.extend` (also from an empty cache)
+appends first and attends to the quantised rows, its own tokens' included, as every decode
+step does.
 """
 from __future__ import annotations
 
@@ -56,17 +65,33 @@ def _check_generative(cfg: NativeConfig) -> None:
                          "(the reference post-LN cross-attention model is not a generator)")
 
 
+KV_FORMATS = ("bf16", "int8")
+
+
+def _check_kv(kv: str) -> str:
+    if kv not in KV_FORMATS:
+        raise ValueError(f"KV cache format must be one of {KV_FORMATS}, got {kv!r}")
+    return kv
+
+
 class KVCache:
     """Per-layer K / V rows ``[B, max_len, Hkv * Dh]`` (K after RoPE) plus the number of
     valid rows: ``lens`` (int32 [B], on the device, what the decode kernel reads) and
-    ``pos`` (the same number on the host; the sequences of a batch advance together)."""
+    ``pos`` (the same number on the host; the sequences of a batch advance together).
 
-    def __init__(self, cfg: NativeConfig, B: int, max_len: int, device, dtype=torch.bfloat16):
+    ``kv="bf16"`` (the default) keeps the rows in ``dtype``; ``kv="int8"`` keeps them as int8
+    ``[B, max_len, W]`` rows with their scales inside (``W = ops.generate.kv8_row_bytes(Hkv,
+    Dh)``).  ``nbytes``: the bytes of all K / V rows of either kind."""
+
+    def __init__(self, cfg: NativeConfig, B: int, max_len: int, device, dtype=torch.bfloat16, kv: str = "bf16"):
         if max_len < 1 or max_len > cfg.max_seq_len:
             raise ValueError(f"KVCache: max_len {max_len} outside [1, max_seq_len = {cfg.max_seq_len}]")
+        self.kv = _check_kv(kv)
         self.B, self.max_len = int(B), int(max_len)
         self.device = torch.device(device)
         kv = cfg.n_kv_heads * cfg.head_dim
+        if self.kv == "int8":
+            kv, dtype = ops.generate.kv8_row_bytes(cfg.n_kv_heads, cfg.head_dim), torch.int8
         self.k: List[torch.Tensor] = [torch.zeros(B, max_len, kv, device=self.device, dtype=dtype)
                                       for _ in range(cfg.n_layers)]
         self.v: List[torch.Tensor] = [torch.zeros(B, max_len, kv, device=self.device, dtype=dtype)
@@ -79,6 +104,10 @@ class KVCache:
         # current decode step began -- where that step's token is embedded and appended
         self.ragged = False
         self.positions = torch.zeros(B, device=self.device, dtype=torch.int32)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.k + self.v)
 
     def reset(self) -> None:
         self.lens.zero_()
@@ -271,12 +300,16 @@ class Generator:
     SwiGLU models only.  ``weights="int4g128"``: the same with 4-bit values and one scale per
     128-element group of K (:func:`ops.quantize_w4`, :func:`ops.linear_w4`); every quantised
     matrix then needs ``K % 128 == 0``.  ``skinny=True`` (bf16 weights on the GPU only): linear layers of at
-    most 16 rows run the bf16 instantiation of the same kernel instead of the training GEMM."""
+    most 16 rows run the bf16 instantiation of the same kernel instead of the training GEMM.
+
+    ``kv_cache="int8"``: the caches :meth:`new_cache` makes (and so those of the ``generate*``
+    methods) hold int8 rows (:class:`KVCache`); any kind of weights."""
 
     def __init__(self, cfg: NativeConfig, device, dtype=torch.bfloat16, seed: int = 0, init: bool = True,
-                 weights: str = "bf16", skinny: bool = False):
+                 weights: str = "bf16", skinny: bool = False, kv_cache: str = "bf16"):
         _check_generative(cfg)
         _check_weights(weights, skinny)
+        self.kv_cache = _check_kv(kv_cache)
         cfg = dataclasses.replace(cfg, dropout=0.0)
         if weights != "bf16":
             qw = QuantWeights(cfg, device, dtype, weights)
@@ -315,7 +348,8 @@ class Generator:
 
     # ------------------------------------------------------------------ constructors
     @classmethod
-    def from_model(cls, model: NativeModel, weights: str = "bf16", skinny: bool = False) -> "Generator":
+    def from_model(cls, model: NativeModel, weights: str = "bf16", skinny: bool = False,
+                   kv_cache: str = "bf16") -> "Generator":
         """Wrap an existing single-stage model (``trainer.stages[0].model`` at ``pp = 1``).
         With bf16 weights they are the model's arena itself: nothing is copied, and a later
         optimizer step is seen by the generator.  ``weights="int8"`` / ``"int4g128"`` take a quantised
@@ -326,6 +360,7 @@ class Generator:
         if model.num_stages != 1 or model.split_head:
             raise ValueError("Generator.from_model needs a single-stage model that owns its LM head (pp = 1)")
         self = cls.__new__(cls)
+        self.kv_cache = _check_kv(kv_cache)
         if weights != "bf16":
             qw = QuantWeights(dataclasses.replace(model.cfg, dropout=0.0), model.device, model.arena.dtype, weights)
             with model.arena.unsharded():
@@ -338,7 +373,8 @@ class Generator:
         return self
 
     @classmethod
-    def load(cls, path: str, device=None, dtype=None, weights: str = "bf16", skinny: bool = False) -> "Generator":
+    def load(cls, path: str, device=None, dtype=None, weights: str = "bf16", skinny: bool = False,
+             kv_cache: str = "bf16") -> "Generator":
         """Weights-only load of a checkpoint directory written by ``save_checkpoint`` at any
         PP / DP degree or head mode (the tensors are found by FQN).  Defaults: the GPU in
         bf16 when there is one, else the CPU in f32.  ``weights="int8"`` / ``"int4g128"`` quantise
@@ -351,7 +387,7 @@ class Generator:
         device = torch.device(device)
         if dtype is None:
             dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
-        self = cls(cfg, device, dtype=dtype, init=False, weights=weights, skinny=skinny)
+        self = cls(cfg, device, dtype=dtype, init=False, weights=weights, skinny=skinny, kv_cache=kv_cache)
         if weights != "bf16":
             for name, t in iter_weights(path, self.arena.order):
                 self.arena.put(name, t)
@@ -383,8 +419,10 @@ class Generator:
         return ops.linear(x, w, bias, act=act, residual=residual, out=out)[0]
 
     # ------------------------------------------------------------------ cache
-    def new_cache(self, B: int, max_len: Optional[int] = None) -> KVCache:
-        return KVCache(self.cfg, B, self.cfg.max_seq_len if max_len is None else max_len, self.device, self.dtype)
+    def new_cache(self, B: int, max_len: Optional[int] = None, kv: Optional[str] = None) -> KVCache:
+        """``kv``: "bf16" / "int8"; None = the generator's ``kv_cache``."""
+        return KVCache(self.cfg, B, self.cfg.max_seq_len if max_len is None else max_len, self.device, self.dtype,
+                       kv=self.kv_cache if kv is None else kv)
 
     # ------------------------------------------------------------------ layers
     def _norm(self, x, w, b):
@@ -441,11 +479,16 @@ class Generator:
                 raise ValueError(f"prefill: lens must hold {B} lengths in [1, {S}]")
         H, KV, Dh = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
         x = self._embed(tokens.to(self.device), S, 0)
+        zero = torch.zeros(B, device=self.device, dtype=torch.int32) if cache.kv == "int8" else None
         for li, blk in enumerate(self.blocks):
             qkv = self._qkv(blk, x, S, 0)
             q, k, v = qkv[:, : H * Dh], qkv[:, H * Dh:(H + KV) * Dh], qkv[:, (H + KV) * Dh:]
-            cache.k[li][:, :S].copy_(k.view(B, S, KV * Dh))     # after RoPE: rope_ is in place
-            cache.v[li][:, :S].copy_(v.view(B, S, KV * Dh))
+            if cache.kv == "int8":
+                # the rotated rows, quantised at positions 0 .. S - 1; attn_fwd below reads the exact ones
+                ops.rope_kv_append(qkv, None, None, cache.k[li], cache.v[li], zero, None, H, KV, Dh, rope=False, T=S)
+            else:
+                cache.k[li][:, :S].copy_(k.view(B, S, KV * Dh))     # after RoPE: rope_ is in place
+                cache.v[li][:, :S].copy_(v.view(B, S, KV * Dh))
             o = torch.empty(B * S, H * Dh, device=x.device, dtype=x.dtype)
             lse = torch.empty(B * H * S, device=x.device, dtype=torch.float32)
             ops.attn_fwd(q, k, v, o, lse, B, S, S, H, KV, Dh, True, p_drop=0.0)
@@ -515,13 +558,19 @@ class Generator:
         if active is not None:
             raise ValueError("decode: active needs a ragged cache (prefill(lens=...))")
         H, KV, Dh = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
+        if cache.kv == "int8":
+            cache.positions.copy_(cache.lens)      # = pos in every row: where the quantising append writes
         cache.lens.add_(1)            # the current token is a key too
         x = self._embed(tokens.to(self.device), 1, pos)
         for li, blk in enumerate(self.blocks):
             qkv = self._qkv(blk, x, 1, pos)
             q, k, v = qkv[:, : H * Dh], qkv[:, H * Dh:(H + KV) * Dh], qkv[:, (H + KV) * Dh:]
-            cache.k[li][:, pos].copy_(k)
-            cache.v[li][:, pos].copy_(v)
+            if cache.kv == "int8":
+                ops.rope_kv_append(qkv, None, None, cache.k[li], cache.v[li], cache.positions, None, H, KV, Dh,
+                                   rope=False)
+            else:
+                cache.k[li][:, pos].copy_(k)
+                cache.v[li][:, pos].copy_(v)
             o = torch.empty(B, H * Dh, device=x.device, dtype=x.dtype)
             ops.attn_decode(q, cache.k[li], cache.v[li], cache.lens, o, H, KV, Dh, max_len=pos + 1)
             x2 = self._linear(o, blk.P + "attn.wo.weight", blk.P + "attn.wo.bias", residual=x)

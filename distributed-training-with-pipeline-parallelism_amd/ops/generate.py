@@ -1,6 +1,12 @@
 """The ops of KV-cache generation (csrc/bindings/generate.cpp): single-token and multi-token
 attention over a cache, the fused RoPE + K/V append at a device-side position, and on-device
-sampling with its CPU reference."""
+sampling with its CPU reference.
+
+The int8 KV cache ("kv8", csrc/kernels/attention_kv8.hip): :func:`attn_decode`,
+:func:`attn_append` and :func:`rope_kv_append` take ``torch.int8`` caches ``[B, Smax, W]`` in
+the row format of :func:`kv_quantize` and pick the int8 kernels by the caches' dtype.  The
+format's three functions (:func:`kv8_row_bytes`, :func:`kv_quantize`, :func:`kv_dequantize`)
+are reached as ``ops.generate.<name>``: the names of ``ops`` itself are a pinned table."""
 from __future__ import annotations
 
 import math
@@ -11,6 +17,70 @@ import torch
 from ._base import _ext, _gpu
 
 __all__ = ["attn_decode_plan", "attn_decode", "attn_append_plan", "attn_append", "rope_kv_append", "sample"]
+
+
+# ======================================================================================
+# the int8 KV-cache row: payload | f32 scales | zero padding
+# ======================================================================================
+def kv8_row_bytes(Hkv: int, D: int) -> int:
+    """Bytes ``W`` of one int8 cache row (one token of one sequence, K or V) of ``Hkv`` heads
+    of dim ``D``: ``Hkv * D`` int8 values head-major, ``Hkv`` little-endian f32 scales, zero
+    padding up to a multiple of 16."""
+    return (int(Hkv) * int(D) + 4 * int(Hkv) + 15) // 16 * 16
+
+
+def kv_quantize(x: torch.Tensor, Hkv: int, D: int) -> torch.Tensor:
+    """x ``[..., Hkv * D]`` (the values a float cache would store) -> int8 ``[..., W]`` rows,
+    ``W = kv8_row_bytes(Hkv, D)``.  Per head, all in f32: ``amax = max |x|``, ``scale = amax /
+    127`` (0 for a zero head), ``inv = 127 / amax`` (0 for a zero head), ``q = clamp(
+    round_half_even(x * inv), -127, 127)``; the effective value is ``q * scale``.  -128 is
+    never written.  Pure tensor code, the same bits on every device and in the HIP kernel."""
+    Hkv, D = int(Hkv), int(D)
+    if x.shape[-1] != Hkv * D:
+        raise ValueError(f"kv_quantize: the last dimension must be Hkv * D = {Hkv * D}, got {x.shape[-1]}")
+    lead = x.shape[:-1]
+    xf = x.detach().float().reshape(*lead, Hkv, D)
+    amax = xf.abs().amax(dim=-1)
+    # tensor divisors: dividing by a Python scalar is a multiplication by its reciprocal on the
+    # GPU, an ulp away from the CPU's quotient in some rows (the rule of quantize_w8)
+    c127 = torch.full_like(amax, 127.0)
+    scale = amax / c127
+    inv = torch.where(amax > 0, c127 / torch.where(amax > 0, amax, torch.ones_like(amax)), torch.zeros_like(amax))
+    q = torch.round(xf * inv[..., None]).clamp_(-127, 127).to(torch.int8)
+    out = torch.zeros(*lead, kv8_row_bytes(Hkv, D), dtype=torch.int8, device=x.device)
+    out[..., : Hkv * D] = q.reshape(*lead, Hkv * D)
+    out[..., Hkv * D: Hkv * D + 4 * Hkv] = scale.contiguous().view(torch.int8)
+    return out
+
+
+def kv_dequantize(rows: torch.Tensor, Hkv: int, D: int, dtype=torch.float32) -> torch.Tensor:
+    """int8 rows ``[..., W]`` of :func:`kv_quantize` -> their effective values ``[..., Hkv * D]``
+    (``q * scale`` in f32, then rounded to ``dtype``)."""
+    Hkv, D = int(Hkv), int(D)
+    if rows.dtype != torch.int8 or rows.shape[-1] != kv8_row_bytes(Hkv, D):
+        raise ValueError(f"kv_dequantize: rows must be int8 [..., {kv8_row_bytes(Hkv, D)}], got {rows.dtype} "
+                         f"{tuple(rows.shape)}")
+    lead = rows.shape[:-1]
+    q = rows[..., : Hkv * D].float().reshape(*lead, Hkv, D)
+    scale = rows[..., Hkv * D: Hkv * D + 4 * Hkv].clone(memory_format=torch.contiguous_format).view(torch.float32)
+    return (q * scale[..., None]).reshape(*lead, Hkv * D).to(dtype)
+
+
+def _kv8(fn: str, k_cache: torch.Tensor, v_cache: torch.Tensor, Hkv: int, D: int) -> bool:
+    """True for a pair of int8 caches (checked: both int8, rows of ``W`` bytes)."""
+    if k_cache.dtype != torch.int8 and v_cache.dtype != torch.int8:
+        return False
+    W = kv8_row_bytes(Hkv, D)
+    if k_cache.dtype != v_cache.dtype or k_cache.shape[-1] != W or v_cache.shape[-1] != W:
+        raise ValueError(f"{fn}: int8 caches are a pair of [B, Smax, {W}] tensors (kv8_row_bytes(Hkv, D) bytes per "
+                         f"row), got {k_cache.dtype} {tuple(k_cache.shape)} and {v_cache.dtype} {tuple(v_cache.shape)}")
+    return True
+
+
+def _cache_rows_f32(cache: torch.Tensor, b: int, n: int, Hkv: int, D: int, kv8: bool) -> torch.Tensor:
+    """the first n rows of sequence b as f32 [Hkv, n, D] (the CPU reference paths)"""
+    rows = kv_dequantize(cache[b, :n], Hkv, D) if kv8 else cache[b, :n, : Hkv * D].float()
+    return rows.reshape(n, Hkv, D).permute(1, 0, 2)
 
 
 def attn_decode_plan(B: int, Hkv: int, max_len: int) -> int:
@@ -37,6 +107,7 @@ def attn_decode(q, k_cache, v_cache, lens, o, H: int, Hkv: int, D: int, scale: O
         raise ValueError("attn_decode: lens must be an int32 tensor on q's device")
     B, Smax = q.shape[0], k_cache.shape[1]
     max_len = Smax if max_len is None else int(max_len)
+    kv8 = _kv8("attn_decode", k_cache, v_cache, Hkv, D)
     if _gpu(q):
         _ext().attn_decode(q, k_cache, v_cache, lens, o, int(H), int(Hkv), int(D), max_len, float(scale), int(splits))
         return o
@@ -47,8 +118,8 @@ def attn_decode(q, k_cache, v_cache, lens, o, H: int, Hkv: int, D: int, scale: O
             o[b, : H * D].zero_()
             continue
         Q = q[b, : H * D].float().reshape(H, 1, D)
-        K = k_cache[b, :n, : Hkv * D].float().reshape(n, Hkv, D).permute(1, 0, 2).repeat_interleave(rep, 0)
-        V = v_cache[b, :n, : Hkv * D].float().reshape(n, Hkv, D).permute(1, 0, 2).repeat_interleave(rep, 0)
+        K = _cache_rows_f32(k_cache, b, n, Hkv, D, kv8).repeat_interleave(rep, 0)
+        V = _cache_rows_f32(v_cache, b, n, Hkv, D, kv8).repeat_interleave(rep, 0)
         p = torch.softmax((Q @ K.transpose(-1, -2)) * scale, -1)
         o[b, : H * D].copy_((p @ V).reshape(H * D).to(o.dtype))
     return o
@@ -86,6 +157,7 @@ def attn_append(q, k_cache, v_cache, base, counts, o, T: int, H: int, Hkv: int, 
     if counts is not None and (counts.dtype != torch.int32 or counts.device != q.device or counts.numel() != B):
         raise ValueError("attn_append: counts must be an int32 [B] tensor on q's device")
     max_len = Smax if max_len is None else int(max_len)
+    kv8 = _kv8("attn_append", k_cache, v_cache, Hkv, D)
     if _gpu(q):
         _ext().attn_append(q, k_cache, v_cache, base, counts, o, T, int(H), int(Hkv), int(D), max_len, float(scale),
                            int(splits))
@@ -100,8 +172,8 @@ def attn_append(q, k_cache, v_cache, base, counts, o, T: int, H: int, Hkv: int, 
             continue
         n = n0 + c
         Q = q[b * T:b * T + c, : H * D].float().reshape(c, H, D).permute(1, 0, 2)
-        K = k_cache[b, :n, : Hkv * D].float().reshape(n, Hkv, D).permute(1, 0, 2).repeat_interleave(rep, 0)
-        V = v_cache[b, :n, : Hkv * D].float().reshape(n, Hkv, D).permute(1, 0, 2).repeat_interleave(rep, 0)
+        K = _cache_rows_f32(k_cache, b, n, Hkv, D, kv8).repeat_interleave(rep, 0)
+        V = _cache_rows_f32(v_cache, b, n, Hkv, D, kv8).repeat_interleave(rep, 0)
         s = (Q @ K.transpose(-1, -2)) * scale
         hidden = torch.arange(n)[None, :] > (n0 + torch.arange(c))[:, None]
         p = torch.softmax(s.masked_fill(hidden, float("-inf")), -1)
@@ -135,9 +207,10 @@ def rope_kv_append(qkv: torch.Tensor, cos: Optional[torch.Tensor], sin: Optional
         raise ValueError("rope_kv_append: active must be uint8 [B] on qkv's device")
     if rope and (cos is None or sin is None or cos.shape[0] < Smax or sin.shape[0] < Smax):
         raise ValueError(f"rope_kv_append: the RoPE tables need at least Smax = {Smax} rows")
+    if _gpu(qkv) and Dh not in (64, 128):
+        raise ValueError(f"rope_kv_append: head_dim {Dh} is not supported by the HIP kernel (64 or 128)")
+    kv8 = _kv8("rope_kv_append", k_cache, v_cache, Hkv, Dh)
     if _gpu(qkv):
-        if Dh not in (64, 128):
-            raise ValueError(f"rope_kv_append: head_dim {Dh} is not supported by the HIP kernel (64 or 128)")
         _ext().rope_kv_append(qkv, cos if rope else None, sin if rope else None, k_cache, v_cache, pos, active,
                               int(H), int(Hkv), int(Dh), bool(rope), T, counts)
         return qkv
@@ -162,6 +235,11 @@ def rope_kv_append(qkv: torch.Tensor, cos: Optional[torch.Tensor], sin: Optional
         rot = x[:, : H + Hkv]
     if rope:
         qkv[rows, : H * Dh] = rot[:, :H].reshape(-1, H * Dh).to(qkv.dtype)
+    if kv8:
+        # the rows a cache of qkv's dtype would hold, quantised: all W bytes of a row are written
+        k_cache[bb[rows], p[rows]] = kv_quantize(rot[:, H:].reshape(-1, Hkv * Dh).to(qkv.dtype), Hkv, Dh)
+        v_cache[bb[rows], p[rows]] = kv_quantize(x[:, H + Hkv:].reshape(-1, Hkv * Dh).to(qkv.dtype), Hkv, Dh)
+        return qkv
     k_cache[bb[rows], p[rows], : Hkv * Dh] = rot[:, H:].reshape(-1, Hkv * Dh).to(k_cache.dtype)
     v_cache[bb[rows], p[rows], : Hkv * Dh] = x[:, H + Hkv:].reshape(-1, Hkv * Dh).to(v_cache.dtype)
     return qkv

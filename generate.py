@@ -8,6 +8,7 @@
     python generate.py --checkpoint DIR --draft-checkpoint SMALL_DIR --lookahead 4 \
         --prompt "1,2,3;7,8" --max-new-tokens 16
     python generate.py --checkpoint DIR --weights int8 --prompt "1,2,3" --max-new-tokens 16
+    python generate.py --checkpoint DIR --kv-cache int8 --prompt "1,2,3" --max-new-tokens 16
 
 The model configuration comes from the checkpoint's manifest; the weights are found by FQN,
 so a checkpoint written at any PP / DP degree loads into this single process.  Prompts are
@@ -29,6 +30,9 @@ the acceptance rate goes to stderr.
 (int8 weight-only inference; the draft of ``--draft-checkpoint`` follows ``--draft-weights``).
 ``--weights int4g128`` stores them as 4-bit values with one scale per 128-element group of K
 instead (every such matrix needs K % 128 == 0).
+
+``--kv-cache int8`` keeps the K / V cache as int8 rows with one f32 scale per (token, KV head):
+about half the cache bytes, with any ``--weights`` (the draft follows ``--draft-kv-cache``).
 """
 from __future__ import annotations
 
@@ -64,13 +68,16 @@ def main(argv=None) -> int:
                     "(per output row / 4-bit with one scale per 128 k)")
     ap.add_argument("--draft-weights", choices=("bf16", "int8", "int4g128"), default="bf16",
                     help="the same for the draft model")
+    ap.add_argument("--kv-cache", choices=("bf16", "int8"), default="bf16",
+                    help="int8: K / V cache rows as int8 with one f32 scale per (token, KV head)")
+    ap.add_argument("--draft-kv-cache", choices=("bf16", "int8"), default="bf16", help="the same for the draft model")
     a = ap.parse_args(argv)
 
     import torch
     import mipipe
 
     rows = parse_prompts(a.prompt)
-    gen = mipipe.Generator.load(a.checkpoint, device=a.device, weights=a.weights)
+    gen = mipipe.Generator.load(a.checkpoint, device=a.device, weights=a.weights, kv_cache=a.kv_cache)
     bad = [t for r in rows for t in r if not 0 <= t < gen.cfg.vocab_size]
     if bad:
         raise ValueError(f"--prompt: token id {bad[0]} outside the vocabulary [0, {gen.cfg.vocab_size})")
@@ -78,7 +85,8 @@ def main(argv=None) -> int:
         if a.temperature != 0 or a.top_k is not None or a.top_p is not None or a.stop_token is not None:
             raise ValueError("--draft-checkpoint: speculative decoding is greedy only (no --temperature / --top-k / "
                              "--top-p / --stop-token)")
-        draft = mipipe.Generator.load(a.draft_checkpoint, device=gen.device, dtype=gen.dtype, weights=a.draft_weights)
+        draft = mipipe.Generator.load(a.draft_checkpoint, device=gen.device, dtype=gen.dtype, weights=a.draft_weights,
+                                      kv_cache=a.draft_kv_cache)
         out, lengths, stats = gen.generate_speculative([torch.tensor(r, dtype=torch.int64) for r in rows],
                                                        a.max_new_tokens, draft, lookahead=a.lookahead,
                                                        pad_token=a.pad_token or 0)
