@@ -217,9 +217,9 @@ void transpose_batched(torch::Tensor src, torch::Tensor dst, torch::Tensor desc,
         "transpose_batched");
 }
 
-// y[M, N] = epi(x[M, K] @ What^T), M <= 16 (csrc/kernels/gemv_skinny.hip): w int8 [N, K] with scale f32 [N],
-// w uint8 [N, K / 2] (packed 4-bit) with scale f32 [K / 128, N], or w bf16 [N, K] without.  No allocation, no
-// synchronisation.
+// y[M, N] = epi(x[M, K] @ What^T), M <= 16 (csrc/kernels/gemv_skinny.hip) or 17 <= M <= 64 (gemv_rows64.hip: the
+// same rows bit for bit): w int8 [N, K] with scale f32 [N], w uint8 [N, K / 2] (packed 4-bit) with scale f32
+// [K / 128, N], or w bf16 [N, K] without.  No allocation, no synchronisation.
 void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> scale, torch::Tensor y,
                  c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, bool gelu,
                  int64_t force_split) {
@@ -238,7 +238,7 @@ void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> 
   TORCH_CHECK((w8 || w4) == scale.has_value(), "gemv_skinny: int8 and 4-bit weights take a scale, bf16 weights none");
   const int code = w4 ? 0 : w8 ? 1 : 2;
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(M >= 1 && M <= gemv::MAX_M, "gemv_skinny: M = ", M, " outside [1, ", gemv::MAX_M, "]");
+  TORCH_CHECK(M >= 1 && M <= gemv::MAX_M_ROWS64, "gemv_skinny: M = ", M, " outside [1, ", gemv::MAX_M_ROWS64, "]");
   TORCH_CHECK(w.size(1) * (w4 ? 2 : 1) == K && y.size(0) == M && y.size(1) == N, "gemv_skinny: shapes x ", x.sizes(), " w ",
               w.sizes(), " y ", y.sizes());
   TORCH_CHECK(gemv::plan(N, K, code, (int)force_split).rows != 0, "gemv_skinny: N = ", N, ", K = ", K,
@@ -266,9 +266,10 @@ void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> 
     TORCH_CHECK(residual->size(0) == M && residual->size(1) == N, "gemv_skinny: residual must be [M, N]");
     ldr = residual->stride(0);
   }
-  check(mp_gemv_skinny(w.data_ptr(), code != 2 ? scale->data_ptr<float>() : nullptr, code, x.data_ptr(), y.data_ptr(),
-                       ptr_or_null(bias), ptr_or_null(residual), (int)M, (int)N, (int)K, x.stride(0), y.stride(0), ldr,
-                       gelu ? 1 : 0, (int)force_split, cur_stream()),
+  const auto kernel = M <= gemv::MAX_M ? mp_gemv_skinny : mp_gemv_rows64;
+  check(kernel(w.data_ptr(), code != 2 ? scale->data_ptr<float>() : nullptr, code, x.data_ptr(), y.data_ptr(),
+               ptr_or_null(bias), ptr_or_null(residual), (int)M, (int)N, (int)K, x.stride(0), y.stride(0), ldr,
+               gelu ? 1 : 0, (int)force_split, cur_stream()),
         "gemv_skinny");
 }
 

@@ -1,0 +1,124 @@
+// Arguments and per-lane operand fragments shared by the weight-streaming linear kernels
+// (csrc/kernels/gemv_skinny.hip: up to 16 x rows; csrc/kernels/gemv_rows64.hip: 17 .. 64).
+// Both read a step's weights the same way and feed the same k to the same MFMA slot, which
+// is what makes a row of their results bitwise equal.
+#pragma once
+#include "mp_common.h"
+
+namespace mp {
+
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+
+struct GemvArgs {
+  const void* w;          // [N, K] int8 or bf16 or [N, K / 2] packed 4-bit, row-major, rows 16-byte aligned
+  const float* scale;     // [N] (int8), [K / 128, N] (4-bit) or null
+  const bf16_t* x;        // [M, ldx]
+  bf16_t* y;              // [M, ldy]
+  const bf16_t* bias;     // [N] or null
+  const bf16_t* res;      // [M, ldr] or null
+  int M, N, K, gelu;
+  int64_t ldx, ldy, ldr;
+};
+
+// the lane's 32 weights of one step as four MFMA fragments
+template <typename WT>
+struct WFrag;
+template <>
+struct WFrag<bf16_t> {
+  u16x8 v[4];
+  __device__ __forceinline__ void load(const bf16_t* p) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const u16x8*>(p + 8 * j);
+  }
+  __device__ __forceinline__ void zero() {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (u16x8)(0);
+  }
+  __device__ __forceinline__ bf16x8 frag(int j) const { return __builtin_bit_cast(bf16x8, v[j]); }
+};
+template <>
+struct WFrag<int8_t> {
+  u32x4 v[2];
+  __device__ __forceinline__ void load(const int8_t* p) {
+    v[0] = *reinterpret_cast<const u32x4*>(p);
+    v[1] = *reinterpret_cast<const u32x4*>(p + 16);
+  }
+  __device__ __forceinline__ void zero() { v[0] = v[1] = (u32x4)(0u); }
+  // bytes + 128 are unsigned (v_cvt_f32_ubyteN), minus 128 is exact in f32, and an integer of
+  // magnitude <= 128 keeps all its bits in the upper half of the f32 word
+  static __device__ __forceinline__ uint32_t pair(uint32_t u, int lo) {
+    const float a = (float)((u >> (8 * lo)) & 0xffu) - 128.0f;
+    const float b = (float)((u >> (8 * lo + 8)) & 0xffu) - 128.0f;
+    return (__float_as_uint(a) >> 16) | (__float_as_uint(b) & 0xffff0000u);
+  }
+  __device__ __forceinline__ bf16x8 frag(int j) const {
+    const uint32_t d0 = v[j >> 1][2 * (j & 1)] ^ 0x80808080u, d1 = v[j >> 1][2 * (j & 1) + 1] ^ 0x80808080u;
+    u32x4 r = {pair(d0, 0), pair(d0, 2), pair(d1, 0), pair(d1, 2)};
+    return __builtin_bit_cast(bf16x8, r);
+  }
+};
+
+// the lane's 32 x values of one step; XA: 16-byte aligned rows (vector loads)
+template <bool XA>
+struct XFrag {
+  u16x8 v[4];
+  __device__ __forceinline__ void load(const bf16_t* p, bool on) {
+    if (!on) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = (u16x8)(0);
+      return;
+    }
+    if constexpr (XA) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const u16x8*>(p + 8 * j);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[j][e] = p[8 * j + e];
+    }
+  }
+  __device__ __forceinline__ bf16x8 frag(int j) const { return __builtin_bit_cast(bf16x8, v[j]); }
+};
+
+// ---- 4-bit weights, one scale per 128 k (int4g128) ------------------------------------------
+// Byte b of a row holds k = 2 b in its low nibble and k = 2 b + 1 in its high one, each as
+// q + 8, so nibble t of a little-endian 32-bit word is the word's k = t.  Lane (i, c) reads the
+// 16 bytes of its 32 k as one load; word j feeds MFMA j.  (u >> (4 t - 3)) & 0x00780078 puts
+// nibbles t and t + 4 of a word into mantissa bits 3..6 of the two halves of a dword, and
+// | 0x41804180 makes each half the bf16 16 + nibble = q + 24 exactly: a shift and a
+// v_and_or_b32 per two weights.  The fragment's slots then hold the word's k in the order
+// 0 4 1 5 2 6 3 7, and the x fragment is permuted to that order once per step for all G row
+// groups.  The offset is taken out by the MFMAs themselves: a constant operand of -24 gives
+// the tile -24 sum_k x[m, k] of the step (the same for every weight row, so once per step),
+// and each row group's MFMAs accumulate on a copy of it.  Every product is an exact bf16 x
+// bf16 one, the group's sum is the MFMA's f32 accumulation, and sum_k x (q + 24) - 24 sum_k x
+// is the group's sum_k x q to f32 rounding of terms 24 / |q| larger than its own.
+struct W4Frag {
+  u32x4 v;
+  __device__ __forceinline__ void load(const uint8_t* p) { v = *reinterpret_cast<const u32x4*>(p); }
+  __device__ __forceinline__ bf16x8 frag(int j) const {
+    const uint32_t u = v[j];
+    u32x4 r = {((u << 3) & 0x00780078u) | 0x41804180u, ((u >> 1) & 0x00780078u) | 0x41804180u,
+               ((u >> 5) & 0x00780078u) | 0x41804180u, ((u >> 9) & 0x00780078u) | 0x41804180u};
+    return __builtin_bit_cast(bf16x8, r);
+  }
+};
+
+// the four scales of the lane's rows n .. n + 3 of one group (sg: that group's row of the
+// [K / 128, N] table); SV: N % 4 == 0 and a 16-byte aligned table, so the four are one load.
+// No branches: rows past N re-read the last rows of the group (in bounds), as the weights do,
+// and their results are never stored.
+template <bool SV>
+__device__ __forceinline__ f32x4 w4_scales(const float* sg, int64_t n, int64_t N) {
+  if constexpr (SV) {
+    return *reinterpret_cast<const f32x4*>(sg + min(n, N - 4));
+  } else {
+    f32x4 s;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s[r] = sg[min(n + r, N - 1)];
+    return s;
+  }
+}
+
+}  // namespace mp

@@ -66,4 +66,19 @@ inline Plan plan(int64_t N, int64_t K, int wbytes, int force_split = 0) {
   return p;
 }
 
+// The 17 .. 64-row sibling (csrc/kernels/gemv_rows64.hip).  Its K-chains are plan()'s -- the
+// same `ksplit` waves over the same steps, which makes a row of its result bitwise the skinny
+// kernel's -- but a workgroup owns at most 32 weight rows: a wave keeps 16 G x 16 MT
+// accumulators and one converted step of weights beside the staged x rows, and G = 4 at
+// MT = 4 does not leave room for the next step's loads.
+constexpr int MAX_M_ROWS64 = 64;
+
+inline Plan plan_rows64(int64_t N, int64_t K, int wbytes, int M, int force_split = 0) {
+  Plan p = plan(N, K, wbytes, force_split);
+  if (p.rows == 0 || M <= MAX_M || M > MAX_M_ROWS64) return Plan();
+  if (p.rows > 32) p.rows = 32;
+  p.grid = (N + p.rows - 1) / p.rows;
+  return p;
+}
+
 }  // namespace gemv

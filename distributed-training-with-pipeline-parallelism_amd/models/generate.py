@@ -302,11 +302,17 @@ class Generator:
     matrix then needs ``K % 128 == 0``.  ``skinny=True`` (bf16 weights on the GPU only): linear layers of at
     most 16 rows run the bf16 instantiation of the same kernel instead of the training GEMM.
 
+    ``skinny64=True`` (off by default): linear layers of 17 to 64 rows -- a batched decode, the
+    verifying ``extend`` of speculative decoding, a short prefill -- run the 64-row sibling of
+    that kernel (:func:`ops.quant.linear_skinny64`), whose rows are bit for bit the 16-row
+    kernel's.  Quantised generators then need no dequantisation scratch up to 64 rows; on bf16
+    weights it implies ``skinny=True`` with the bound at 64.
+
     ``kv_cache="int8"``: the caches :meth:`new_cache` makes (and so those of the ``generate*``
     methods) hold int8 rows (:class:`KVCache`); any kind of weights."""
 
     def __init__(self, cfg: NativeConfig, device, dtype=torch.bfloat16, seed: int = 0, init: bool = True,
-                 weights: str = "bf16", skinny: bool = False, kv_cache: str = "bf16"):
+                 weights: str = "bf16", skinny: bool = False, kv_cache: str = "bf16", skinny64: bool = False):
         _check_generative(cfg)
         _check_weights(weights, skinny)
         self.kv_cache = _check_kv(kv_cache)
@@ -316,9 +322,10 @@ class Generator:
             if init:
                 qw.init_params(seed)
             self._bind_quant(qw)
+            self.skinny64 = bool(skinny64)
             return
         self._bind(NativeModel(cfg, 0, 1, torch.device(device), seed=seed, recompute=False, dtype=dtype, init=init))
-        self.skinny = bool(skinny)
+        self.skinny, self.skinny64 = bool(skinny or skinny64), bool(skinny64)
 
     def _bind(self, model: NativeModel) -> None:
         self.model = model
@@ -328,7 +335,7 @@ class Generator:
         self.dtype = model.arena.dtype
         self.blocks: List[Block] = model.blocks
         self.weights = "bf16"
-        self.skinny = False
+        self.skinny = self.skinny64 = False
         self._scratch = None
 
     def _bind_quant(self, qw: QuantWeights) -> None:
@@ -343,13 +350,13 @@ class Generator:
             rope = ops.rope_tables(cfg.max_seq_len, cfg.head_dim, cfg.rope_theta, self.device)
         self.blocks = [_QBlock(i, qw, rope) for i in range(cfg.n_layers)]
         self.weights = qw.fmt
-        self.skinny = False
+        self.skinny = self.skinny64 = False
         self._scratch: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------ constructors
     @classmethod
     def from_model(cls, model: NativeModel, weights: str = "bf16", skinny: bool = False,
-                   kv_cache: str = "bf16") -> "Generator":
+                   kv_cache: str = "bf16", skinny64: bool = False) -> "Generator":
         """Wrap an existing single-stage model (``trainer.stages[0].model`` at ``pp = 1``).
         With bf16 weights they are the model's arena itself: nothing is copied, and a later
         optimizer step is seen by the generator.  ``weights="int8"`` / ``"int4g128"`` take a quantised
@@ -367,14 +374,15 @@ class Generator:
                 for n in qw.order:
                     qw.put(n, model.arena.master_view(n))
             self._bind_quant(qw)
+            self.skinny64 = bool(skinny64)
             return self
         self._bind(model)
-        self.skinny = bool(skinny)
+        self.skinny, self.skinny64 = bool(skinny or skinny64), bool(skinny64)
         return self
 
     @classmethod
     def load(cls, path: str, device=None, dtype=None, weights: str = "bf16", skinny: bool = False,
-             kv_cache: str = "bf16") -> "Generator":
+             kv_cache: str = "bf16", skinny64: bool = False) -> "Generator":
         """Weights-only load of a checkpoint directory written by ``save_checkpoint`` at any
         PP / DP degree or head mode (the tensors are found by FQN).  Defaults: the GPU in
         bf16 when there is one, else the CPU in f32.  ``weights="int8"`` / ``"int4g128"`` quantise
@@ -387,7 +395,8 @@ class Generator:
         device = torch.device(device)
         if dtype is None:
             dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
-        self = cls(cfg, device, dtype=dtype, init=False, weights=weights, skinny=skinny, kv_cache=kv_cache)
+        self = cls(cfg, device, dtype=dtype, init=False, weights=weights, skinny=skinny, kv_cache=kv_cache,
+                   skinny64=skinny64)
         if weights != "bf16":
             for name, t in iter_weights(path, self.arena.order):
                 self.arena.put(name, t)
@@ -403,19 +412,23 @@ class Generator:
         if self.weights != "bf16":
             key = A.head_name if wname == "lm_head" else wname
             q, scale = A.q[key], A.scale[key]
-            scratch, kmult = None, ops.QUANT_FORMATS[self.weights].k_skinny
-            if x.is_cuda and (x.shape[0] > ops.W8_SKINNY_MAX_M or x.shape[1] % kmult != 0):
+            scratch = None
+            if x.is_cuda and not ops.quant.reads_weights_directly(x, self.weights, self.skinny64):
                 if self._scratch is None:
                     if torch.cuda.is_current_stream_capturing():
                         raise RuntimeError("Generator: the dequantisation scratch cannot be allocated inside a graph "
                                            "capture (run one step eagerly first)")
                     self._scratch = torch.empty(A.max_matrix_numel(), device=self.device, dtype=torch.bfloat16)
                 scratch = self._scratch
-            return ops.linear_q(x, q, scale, self.weights, bias, act, residual, out, scratch=scratch)
+            return ops.linear_q(x, q, scale, self.weights, bias, act, residual, out, scratch=scratch,
+                                rows64=self.skinny64)
         w = self.model.head_weight() if wname == "lm_head" else A.w(wname)
-        if self.skinny and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[0] <= ops.SKINNY_MAX_M \
-                and w.shape[1] % 32 == 0 and act in ("none", "gelu", "gelu_tanh"):
-            return ops.linear_skinny(x, w, None, bias, act, residual, out)
+        if self.skinny and x.is_cuda and x.dtype == torch.bfloat16 and w.shape[1] % 32 == 0 \
+                and act in ("none", "gelu", "gelu_tanh"):
+            if x.shape[0] <= ops.SKINNY_MAX_M:
+                return ops.linear_skinny(x, w, None, bias, act, residual, out)
+            if self.skinny64 and ops.quant.reads_weights_directly(x, "int8", True):
+                return ops.quant.linear_skinny64(x, w, None, bias, act, residual, out)
         return ops.linear(x, w, bias, act=act, residual=residual, out=out)[0]
 
     # ------------------------------------------------------------------ cache

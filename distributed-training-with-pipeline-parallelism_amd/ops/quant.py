@@ -16,10 +16,14 @@ __all__ = ["SKINNY_MAX_M", "W8_SKINNY_MAX_M", "W4_GROUP", "QUANT_FORMATS", "quan
 
 SKINNY_MAX_M = 16
 # linear_w8 runs the skinny kernel up to this many rows and dequantises above.  16 = one call
-# of the kernel; looping it over 16-row blocks has not been measured against the
-# dequantising route (tools/w8_time.py prints both, profiles/r12_w8_decode.md)
+# of the kernel.  Looping it over 16-row blocks and the 64-row kernel behind rows64=True are
+# both measured against the dequantising route by tools/w8_time.py (profiles/r15_rows64.md);
+# the default route is unchanged
 W8_SKINNY_MAX_M = 16
 W4_GROUP = 128
+# rows of one call of the 64-row sibling (csrc/kernels/gemv_rows64.hip): linear_skinny64, and
+# linear_q(rows64=True) between W8_SKINNY_MAX_M and this.  A name of this module only
+SKINNY64_MAX_M = 64
 
 
 def gemv_plan(N: int, K: int, wbytes: int, force_split: int = 0) -> Tuple[int, int]:
@@ -177,28 +181,51 @@ def _linear_cpu(f, x, q, scale, bias, act, residual, out):
     return out.copy_(y.to(out.dtype))
 
 
-def _skinny(f, x, q, scale, bias, act, residual, out, force_split, checked=None):
-    M, N, K, out = checked or _checked(f.skinny, f, x, q, scale, bias, act, residual, out)
-    if M < 1 or M > SKINNY_MAX_M:
-        raise ValueError(f"{f.skinny}: M = {M} outside [1, {SKINNY_MAX_M}] ({f.any_m})")
+def _skinny(f, x, q, scale, bias, act, residual, out, force_split, checked=None, name=None, max_m=SKINNY_MAX_M):
+    name = name or f.skinny
+    M, N, K, out = checked or _checked(name, f, x, q, scale, bias, act, residual, out)
+    if M < 1 or M > max_m:
+        raise ValueError(f"{name}: M = {M} outside [1, {max_m}] ({f.any_m})")
     if K % f.k_skinny != 0:
-        raise ValueError(f"{f.skinny}: K = {K} must be a multiple of {f.k_skinny}")
+        raise ValueError(f"{name}: K = {K} must be a multiple of {f.k_skinny}")
     if not _gpu(x):
         return _linear_cpu(f, x, q, scale, bias, act, residual, out)
+    if M > SKINNY_MAX_M and not _x_aligned(x):
+        raise ValueError(f"{name}: more than {SKINNY_MAX_M} rows need 16-byte aligned x rows (the data pointer and "
+                         f"a row stride of a multiple of 8 elements)")
     _ext().gemv_skinny(x, q, scale, out, bias, residual, act != "none", int(force_split))
     return out
 
 
+def _x_aligned(x):
+    """x rows the 64-row kernel can read as 16-byte chunks"""
+    return x.data_ptr() % 16 == 0 and x.stride(0) % 8 == 0 and x.stride(1) == 1
+
+
+def reads_weights_directly(x: torch.Tensor, fmt: str, rows64: bool = False) -> bool:
+    """Whether :func:`linear_q` runs a GPU ``x`` [M, K] on the quantised matrix itself (the
+    skinny kernel, or with ``rows64`` its 64-row sibling) and so needs no scratch.  The one
+    statement of that route: ``linear_q`` and the generator both ask here."""
+    M, K = x.shape
+    if K % QUANT_FORMATS[fmt].k_skinny != 0:
+        return False
+    return M <= W8_SKINNY_MAX_M or (rows64 and M <= SKINNY64_MAX_M and _x_aligned(x))
+
+
 def linear_q(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, fmt: str, bias: Optional[torch.Tensor] = None,
              act: str = "none", residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-             scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """:func:`linear_w8` / :func:`linear_w4` by the name of the format, a key of ``QUANT_FORMATS``."""
+             scratch: Optional[torch.Tensor] = None, rows64: bool = False) -> torch.Tensor:
+    """:func:`linear_w8` / :func:`linear_w4` by the name of the format, a key of ``QUANT_FORMATS``.
+    ``rows64=True``: on the GPU, ``W8_SKINNY_MAX_M < M <= SKINNY64_MAX_M`` rows (16-byte aligned,
+    ``K`` a multiple of the format's skinny step) run :func:`linear_skinny64` on the quantised
+    matrix itself instead of dequantising: no scratch is touched."""
     f = QUANT_FORMATS[fmt]
     M, N, K, out = _checked(f.linear, f, x, q, scale, bias, act, residual, out)
     if not _gpu(x):
         return _linear_cpu(f, x, q, scale, bias, act, residual, out)
-    if M <= W8_SKINNY_MAX_M and K % f.k_skinny == 0:
-        return _skinny(f, x, q, scale, bias, act, residual, out, 0, checked=(M, N, K, out))
+    if reads_weights_directly(x, fmt, rows64):
+        return _skinny(f, x, q, scale, bias, act, residual, out, 0, checked=(M, N, K, out),
+                       max_m=SKINNY64_MAX_M if rows64 else SKINNY_MAX_M)
     if scratch is None:
         scratch = torch.empty(N * K, device=x.device, dtype=torch.bfloat16)
     if scratch.dtype != torch.bfloat16 or scratch.numel() < N * K or not scratch.is_contiguous():
@@ -218,6 +245,20 @@ def linear_skinny(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor
     rows or on the other rows.  ``force_split``: the K-split of the plan, for tests.  No host
     synchronisation and, given ``out``, no allocation.  Returns y."""
     return _skinny(QUANT_FORMATS["int8"], x, w, scale, bias, act, residual, out, force_split)
+
+
+def linear_skinny64(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                    bias: Optional[torch.Tensor] = None, act: str = "none", residual: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None, force_split: int = 0) -> torch.Tensor:
+    """:func:`linear_skinny` / :func:`linear_skinny_w4` for up to ``SKINNY64_MAX_M`` = 64 rows, by
+    the dtype of ``w``: int8 [N, K] with ``scale`` [N], uint8 packed 4-bit [N, K / 2] with
+    ``scale`` [K / 128, N], or bf16 [N, K] without a scale.  Above 16 rows the weights are still
+    streamed and converted once (csrc/kernels/gemv_rows64.hip), and row m of the result is bit
+    for bit what the 16-row call gives for that row, for every M, epilogue and ``force_split``:
+    the K-chains of the plan do not change.  More than 16 rows need 16-byte aligned x rows.
+    Everything else is as in :func:`linear_skinny`.  Returns y."""
+    f = QUANT_FORMATS["int4g128" if w.dtype == torch.uint8 else "int8"]
+    return _skinny(f, x, w, scale, bias, act, residual, out, force_split, name="linear_skinny64", max_m=SKINNY64_MAX_M)
 
 
 def linear_w8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None,

@@ -31,6 +31,10 @@ the acceptance rate goes to stderr.
 ``--weights int4g128`` stores them as 4-bit values with one scale per 128-element group of K
 instead (every such matrix needs K % 128 == 0).
 
+``--skinny64`` runs linear layers of 17 to 64 rows (a batch of up to 64 prompts, the verifying
+pass of speculative decoding, a short prefill) on the 64-row weight-streaming kernel, with any
+``--weights``; off by default.
+
 ``--kv-cache int8`` keeps the K / V cache as int8 rows with one f32 scale per (token, KV head):
 about half the cache bytes, with any ``--weights`` (the draft follows ``--draft-kv-cache``).
 """
@@ -71,13 +75,17 @@ def main(argv=None) -> int:
     ap.add_argument("--kv-cache", choices=("bf16", "int8"), default="bf16",
                     help="int8: K / V cache rows as int8 with one f32 scale per (token, KV head)")
     ap.add_argument("--draft-kv-cache", choices=("bf16", "int8"), default="bf16", help="the same for the draft model")
+    ap.add_argument("--skinny64", action="store_true",
+                    help="linear layers of 17 to 64 rows on the 64-row weight-streaming kernel (no dequantisation "
+                    "scratch for them); also for the draft model")
     a = ap.parse_args(argv)
 
     import torch
     import mipipe
 
     rows = parse_prompts(a.prompt)
-    gen = mipipe.Generator.load(a.checkpoint, device=a.device, weights=a.weights, kv_cache=a.kv_cache)
+    gen = mipipe.Generator.load(a.checkpoint, device=a.device, weights=a.weights, kv_cache=a.kv_cache,
+                                skinny64=a.skinny64)
     bad = [t for r in rows for t in r if not 0 <= t < gen.cfg.vocab_size]
     if bad:
         raise ValueError(f"--prompt: token id {bad[0]} outside the vocabulary [0, {gen.cfg.vocab_size})")
@@ -86,7 +94,7 @@ def main(argv=None) -> int:
             raise ValueError("--draft-checkpoint: speculative decoding is greedy only (no --temperature / --top-k / "
                              "--top-p / --stop-token)")
         draft = mipipe.Generator.load(a.draft_checkpoint, device=gen.device, dtype=gen.dtype, weights=a.draft_weights,
-                                      kv_cache=a.draft_kv_cache)
+                                      kv_cache=a.draft_kv_cache, skinny64=a.skinny64)
         out, lengths, stats = gen.generate_speculative([torch.tensor(r, dtype=torch.int64) for r in rows],
                                                        a.max_new_tokens, draft, lookahead=a.lookahead,
                                                        pad_token=a.pad_token or 0)

@@ -19,11 +19,19 @@ fit there; ``copies`` is printed.  Variants: ``w8`` = ops.linear_w8 (the skinny 
 W8_SKINNY_MAX_M rows, dequantise + ops.linear above), ``w4`` = ops.linear_w4 on the int4g128
 format of the same weights (the same routes), ``skinny_bf16`` (up to 16 rows),
 ``linear`` = ops.linear on bf16 weights, ``dequant_linear`` = dequant_w8 + ops.linear at every
-M (the crossover).  GB/s counts the weight bytes of the variant's own format once per call
-(for ``w4`` the packed nibbles and their group scales: N K / 2 + N K / 32 bytes).
+M (the crossover).  Above 16 and up to 64 rows four more alternate in the same windows:
+``rows64`` / ``rows64_w4`` / ``rows64_bf16`` = ops.quant.linear_skinny64 on the int8 / int4g128 /
+bf16 weights (csrc/kernels/gemv_rows64.hip) and ``loop`` = ceil(M / 16) ``linear_skinny`` calls
+on the int8 weights, which reads and converts them that many times.  Every record also carries
+``<variant>_spread_us``, the largest minus the smallest window.  MIPIPE_EXT_VARIANT=xreg (a
+``tools/build_ext.py --variant xreg -DMP_ROWS64_XREG`` build) times the register-direct x path
+of the 64-row kernel in a process of its own.  GB/s counts the weight bytes of the variant's
+own format once per call (for ``w4`` the packed nibbles and their group scales: N K / 2 +
+N K / 32 bytes).
 
 End to end (``--parts e2e``): greedy ``generate_batch`` (eager step) of one set of weights as
-a bf16 generator, the same with ``skinny=True`` and quantised to int8 and to int4g128;
+a bf16 generator, the same with ``skinny=True`` and quantised to int8 and to int4g128, and the
+bf16 and int8 ones again with ``skinny64=True`` (they differ from 17 sequences on);
 ``--speculative`` adds ``generate_speculative`` of the bf16 target with its own int8 and
 int4g128 generators as the draft.  A
 window is one whole call (prefill + new tokens); tok/s = B * new_tokens / median.
@@ -80,7 +88,7 @@ def _windows(variants, windows, iters):
             e.synchronize()
             times[name].append(s.elapsed_time(e) * 1e-3 / iters)
         call += iters
-    return {n: statistics.median(t) for n, t in times.items()}
+    return {n: statistics.median(t) for n, t in times.items()}, {n: max(t) - min(t) for n, t in times.items()}
 
 
 def gemm_part(a, dev):
@@ -104,13 +112,21 @@ def gemm_part(a, dev):
                 }
                 if M <= ops.SKINNY_MAX_M:
                     variants["skinny_bf16"] = lambda i: ops.linear_skinny(x, w[i % copies], out=y)
-                t = _windows(variants, a.windows, a.iters)
+                if ops.SKINNY_MAX_M < M <= ops.quant.SKINNY64_MAX_M:
+                    s64 = ops.quant.linear_skinny64
+                    variants["rows64"] = lambda i: s64(x, *qs[i % copies], out=y)
+                    variants["rows64_w4"] = lambda i: s64(x, *q4s[i % copies], out=y)
+                    variants["rows64_bf16"] = lambda i: s64(x, w[i % copies], out=y)
+                    variants["loop"] = lambda i: [ops.linear_skinny(x[m: m + 16], *qs[i % copies], out=y[m: m + 16])
+                                                  for m in range(0, M, 16)]
+                t, spread = _windows(variants, a.windows, a.iters)
                 rec = {"model": mname, "layer": lname, "N": N, "K": K, "M": M, "copies": copies,
                        "w8_route": "skinny" if M <= ops.W8_SKINNY_MAX_M else "dequant"}
                 for name, sec in t.items():
-                    wbytes = N * K // 2 + N * K // 32 if name == "w4" else \
-                        N * K * (1 if name in ("w8", "dequant_linear") else 2)
+                    wbytes = N * K // 2 + N * K // 32 if name in ("w4", "rows64_w4") else \
+                        N * K * (1 if name in ("w8", "dequant_linear", "rows64", "loop") else 2)
                     rec[f"{name}_us"] = round(sec * 1e6, 1)
+                    rec[f"{name}_spread_us"] = round(spread[name] * 1e6, 1)
                     rec[f"{name}_gbs"] = round(wbytes / sec * 1e-9)
                 print(json.dumps(rec), flush=True)
                 recs.append(rec)
@@ -127,7 +143,9 @@ def e2e_part(a, dev):
         base = mipipe.Generator(cfg, dev, dtype=torch.bfloat16, seed=0)
         gens = {"bf16": base, "bf16_skinny": mipipe.Generator.from_model(base.model, skinny=True),
                 "int8": mipipe.Generator.from_model(base.model, weights="int8"),
-                "int4g128": mipipe.Generator.from_model(base.model, weights="int4g128")}
+                "int4g128": mipipe.Generator.from_model(base.model, weights="int4g128"),
+                "bf16_skinny64": mipipe.Generator.from_model(base.model, skinny64=True),
+                "int8_skinny64": mipipe.Generator.from_model(base.model, weights="int8", skinny64=True)}
         for B in (int(b) for b in a.batches.split(",")):
             prompt = torch.randint(0, cfg.vocab_size, (B, S0), generator=torch.Generator().manual_seed(B))
             rows = list(prompt)
@@ -153,6 +171,10 @@ def e2e_part(a, dev):
             rec["int8_vs_bf16"] = round(rec["int8_tok_s"] / rec["bf16_tok_s"], 3)
             rec["int4g128_vs_bf16"] = round(rec["int4g128_tok_s"] / rec["bf16_tok_s"], 3)
             rec["int4g128_vs_int8"] = round(rec["int4g128_tok_s"] / rec["int8_tok_s"], 3)
+            rec["int8_skinny64_vs_int8"] = round(rec["int8_skinny64_tok_s"] / rec["int8_tok_s"], 3)
+            rec["int8_skinny64_vs_bf16"] = round(rec["int8_skinny64_tok_s"] / rec["bf16_tok_s"], 3)
+            for n in variants:
+                rec[f"{n}_spread_ms"] = round((max(times[n]) - min(times[n])) * 1e3, 2)
             rec["skinny_tokens_equal_bf16"] = bool(torch.equal(outs["bf16"], outs["bf16_skinny"]))
             if a.speculative:
                 st = outs["bf16_spec_int8_draft"][2]
@@ -170,13 +192,14 @@ def e2e_part(a, dev):
 def _markdown(gemm, e2e):
     if gemm:
         print("\n| model | layer | N x K | M | w4 us | w4 GB/s | w8 us | w8 GB/s | skinny bf16 us | GB/s | linear us | GB/s "
-              "| dequant+linear us |")
-        print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+              "| dequant+linear us | rows64 us | rows64 w4 us | rows64 bf16 us | loop us |")
+        print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
         for r in gemm:
             sk = (r.get("skinny_bf16_us", "-"), r.get("skinny_bf16_gbs", "-"))
             print(f"| {r['model']} | {r['layer']} | {r['N']} x {r['K']} | {r['M']} | {r['w4_us']} | {r['w4_gbs']} | "
                   f"{r['w8_us']} ({r['w8_route']}) | "
-                  f"{r['w8_gbs']} | {sk[0]} | {sk[1]} | {r['linear_us']} | {r['linear_gbs']} | {r['dequant_linear_us']} |")
+                  f"{r['w8_gbs']} | {sk[0]} | {sk[1]} | {r['linear_us']} | {r['linear_gbs']} | {r['dequant_linear_us']} | "
+                  + " | ".join(str(r.get(f"{n}_us", "-")) for n in ("rows64", "rows64_w4", "rows64_bf16", "loop")) + " |")
     if e2e:
         keys = [k for k in e2e[0] if k not in ("model", "B", "prompt", "new_tokens")]
         print("\n| model | B | " + " | ".join(keys) + " |")
@@ -190,7 +213,7 @@ def main(argv=None) -> int:
     ap.add_argument("--parts", default="gemm,e2e")
     ap.add_argument("--models", default="gpt2-small,llama3-1b,llama3-8b")
     ap.add_argument("--rows", default="1,4,8,16,32,64")
-    ap.add_argument("--batches", default="1,8")
+    ap.add_argument("--batches", default="1,8,32,64")
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--new-tokens", type=int, default=128)
     ap.add_argument("--windows", type=int, default=5)
