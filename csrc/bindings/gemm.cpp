@@ -219,7 +219,8 @@ void transpose_batched(torch::Tensor src, torch::Tensor dst, torch::Tensor desc,
 
 // y[M, N] = epi(x[M, K] @ What^T), M <= 16 (csrc/kernels/gemv_skinny.hip) or 17 <= M <= 64 (gemv_rows64.hip: the
 // same rows bit for bit): w int8 [N, K] with scale f32 [N], w uint8 [N, K / 2] (packed 4-bit) with scale f32
-// [K / 128, N], or w bf16 [N, K] without.  No allocation, no synchronisation.
+// [K / 128, N] (int4g128) or scale uint8 [N, K / 32] (MXFP4: e8m0 bytes; M <= 16), or w bf16 [N, K] without.
+// No allocation, no synchronisation.
 void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> scale, torch::Tensor y,
                  c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, bool gelu,
                  int64_t force_split) {
@@ -237,6 +238,7 @@ void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> 
               w.scalar_type());
   TORCH_CHECK((w8 || w4) == scale.has_value(), "gemv_skinny: int8 and 4-bit weights take a scale, bf16 weights none");
   const int code = w4 ? 0 : w8 ? 1 : 2;
+  const bool mx4 = w4 && scale->scalar_type() == torch::kUInt8;      // the format is told by the scale's dtype
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(M >= 1 && M <= gemv::MAX_M_ROWS64, "gemv_skinny: M = ", M, " outside [1, ", gemv::MAX_M_ROWS64, "]");
   TORCH_CHECK(w.size(1) * (w4 ? 2 : 1) == K && y.size(0) == M && y.size(1) == N, "gemv_skinny: shapes x ", x.sizes(), " w ",
@@ -249,7 +251,12 @@ void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> 
     req(*scale, torch::kFloat32, "gemv_skinny: scale");
     TORCH_CHECK(scale->numel() == N && scale->is_contiguous(), "gemv_skinny: scale must hold N contiguous values");
   }
-  if (w4) {
+  if (mx4) {
+    req(*scale, torch::kUInt8, "gemv_skinny: scale");
+    TORCH_CHECK(scale->dim() == 2 && scale->size(0) == N && scale->size(1) == K / 32 && scale->is_contiguous(),
+                "gemv_skinny: the scale of MXFP4 weights must be contiguous uint8 [N, K / 32]");
+    TORCH_CHECK(M <= gemv::MAX_M, "gemv_skinny: MXFP4 weights take M <= ", gemv::MAX_M, " rows, got ", M);
+  } else if (w4) {
     req(*scale, torch::kFloat32, "gemv_skinny: scale");
     TORCH_CHECK(scale->dim() == 2 && scale->size(0) == K / gemv::KSTEP && scale->size(1) == N && scale->is_contiguous(),
                 "gemv_skinny: the scale of 4-bit weights must be contiguous [K / 128, N]");
@@ -266,6 +273,13 @@ void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> 
     TORCH_CHECK(residual->size(0) == M && residual->size(1) == N, "gemv_skinny: residual must be [M, N]");
     ldr = residual->stride(0);
   }
+  if (mx4) {
+    check(mp_gemv_mx4(w.data_ptr(), scale->data_ptr<uint8_t>(), x.data_ptr(), y.data_ptr(), ptr_or_null(bias),
+                      ptr_or_null(residual), (int)M, (int)N, (int)K, x.stride(0), y.stride(0), ldr, gelu ? 1 : 0,
+                      (int)force_split, cur_stream()),
+          "gemv_skinny (MXFP4)");
+    return;
+  }
   const auto kernel = M <= gemv::MAX_M ? mp_gemv_skinny : mp_gemv_rows64;
   check(kernel(w.data_ptr(), code != 2 ? scale->data_ptr<float>() : nullptr, code, x.data_ptr(), y.data_ptr(),
                ptr_or_null(bias), ptr_or_null(residual), (int)M, (int)N, (int)K, x.stride(0), y.stride(0), ldr,
@@ -273,10 +287,24 @@ void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> 
         "gemv_skinny");
 }
 
-// q int8 [N, K] with scale [N], or q uint8 [N, K / 2] (packed 4-bit) with scale [K / 128, N]
+// q int8 [N, K] with scale [N], or q uint8 [N, K / 2] (packed 4-bit) with scale f32 [K / 128, N] (int4g128) or
+// uint8 [N, K / 32] (MXFP4)
 void dequant_w8(torch::Tensor q, torch::Tensor scale, torch::Tensor out) {
-  req(scale, torch::kFloat32, "dequant_w8: scale");
   req(out, torch::kBFloat16, "dequant_w8: out");
+  if (scale.scalar_type() == torch::kUInt8) {
+    req(scale, torch::kUInt8, "dequant_w8: scale");
+    req(q, torch::kUInt8, "dequant_w8: q");
+    TORCH_CHECK(q.dim() == 2 && q.is_contiguous() && out.is_contiguous() && out.numel() == 2 * q.numel(),
+                "dequant_w8: packed MXFP4 q [N, K / 2] and out [N, K], both contiguous");
+    const int64_t N = q.size(0), K = 2 * q.size(1);
+    TORCH_CHECK(K >= 128 && K % 128 == 0, "dequant_w8: K = ", K, " must be a multiple of 128 for MXFP4 weights");
+    TORCH_CHECK(scale.is_contiguous() && scale.dim() == 2 && scale.size(0) == N && scale.size(1) == K / 32,
+                "dequant_w8: the scale of MXFP4 weights must be contiguous uint8 [N, K / 32]");
+    check(mp_dequant_mx4(q.data_ptr(), scale.data_ptr<uint8_t>(), out.data_ptr(), N, K, cur_stream()),
+          "dequant_w8 (MXFP4)");
+    return;
+  }
+  req(scale, torch::kFloat32, "dequant_w8: scale");
   if (q.scalar_type() == torch::kUInt8) {
     req(q, torch::kUInt8, "dequant_w8: q");
     TORCH_CHECK(q.dim() == 2 && q.is_contiguous() && out.is_contiguous() && out.numel() == 2 * q.numel(),

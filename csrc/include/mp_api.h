@@ -74,6 +74,10 @@ int mp_gemv_skinny(const void* w, const float* scale, int wbytes, const void* x,
                    int force_split, hipStream_t st);
 int mp_dequant_w8(const void* q, const float* scale, void* out, int64_t N, int64_t K, hipStream_t st);
 int mp_dequant_w4(const void* q, const float* scale, void* out, int64_t N, int64_t K, hipStream_t st);
+// MXFP4: packed e2m1 [N, K / 2] with e8m0 scale bytes [N, K / 32]; M <= 16 only
+int mp_gemv_mx4(const void* w, const uint8_t* scale, const void* x, void* y, const void* bias, const void* res, int M,
+                int N, int K, int64_t ldx, int64_t ldy, int64_t ldr, int gelu, int force_split, hipStream_t st);
+int mp_dequant_mx4(const void* q, const uint8_t* scale, void* out, int64_t N, int64_t K, hipStream_t st);
 // ---- gemv_rows64.hip: the same call for 17 <= M <= 64
 int mp_gemv_rows64(const void* w, const float* scale, int wbytes, const void* x, void* y, const void* bias,
                    const void* res, int M, int N, int K, int64_t ldx, int64_t ldy, int64_t ldr, int gelu,

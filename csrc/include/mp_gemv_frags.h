@@ -11,7 +11,7 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 struct GemvArgs {
   const void* w;          // [N, K] int8 or bf16 or [N, K / 2] packed 4-bit, row-major, rows 16-byte aligned
-  const float* scale;     // [N] (int8), [K / 128, N] (4-bit) or null
+  const float* scale;     // [N] (int8), [K / 128, N] (4-bit), the e8m0 bytes [N, K / 32] of MXFP4 weights, or null
   const bf16_t* x;        // [M, ldx]
   bf16_t* y;              // [M, ldy]
   const bf16_t* bias;     // [N] or null
@@ -119,6 +119,45 @@ __device__ __forceinline__ f32x4 w4_scales(const float* sg, int64_t n, int64_t N
     for (int r = 0; r < 4; ++r) s[r] = sg[min(n + r, N - 1)];
     return s;
   }
+}
+
+// ---- MXFP4 weights: e2m1 nibbles, one e8m0 scale byte per 32 k ---------------------------------
+// The bytes are laid out as int4g128's (byte b of a row = k 2 b low, k 2 b + 1 high), so lane (i, c)
+// again reads the 16 bytes of its 32 k as one load -- and those 32 k are exactly one MX group, so
+// the lane has ONE scale for the step, that of (row i, group 4 s + c), and the scale belongs to
+// the weight operand.  v_cvt_scalef32_pk_bf16_fp4 turns byte `sel` of a dword (two e2m1 codes)
+// into two bf16 values times 2^(exponent of its f32 scale operand), low nibble first: four of
+// them per dword give the word's eight k in natural order, ready for MFMA j against the
+// unpermuted x fragment.  e2m1 x 2^e is exact in bf16 (normal range), so What itself is the operand.
+struct MX4Frag {
+  u32x4 v;
+  __device__ __forceinline__ void load(const uint8_t* p) { v = *reinterpret_cast<const u32x4*>(p); }
+  // sc: 2^(e - 127) as f32 bits, mx4_scale()
+  __device__ __forceinline__ bf16x8 frag(int j, float sc) const {
+    typedef __attribute__((ext_vector_type(2))) __bf16 bfx2;
+    const bfx2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v[j], sc, 0);
+    const bfx2 p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v[j], sc, 1);
+    const bfx2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v[j], sc, 2);
+    const bfx2 p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v[j], sc, 3);
+    const u32x4 r = {__builtin_bit_cast(uint32_t, p0), __builtin_bit_cast(uint32_t, p1),
+                     __builtin_bit_cast(uint32_t, p2), __builtin_bit_cast(uint32_t, p3)};
+    return __builtin_bit_cast(bf16x8, r);
+  }
+};
+
+// the e8m0 byte as the f32 2^(byte - 127): the byte is the f32 exponent field
+__device__ __forceinline__ float mx4_scale(uint32_t byte) { return __uint_as_float(byte << 23); }
+
+// The scale bytes of one step of a row are 4 consecutive bytes at byte 4 s of its scale row
+// (sr: the row's byte 4 s; a row has K / 32 bytes, a multiple of 4).  SA: the table is 4-byte
+// aligned, so they are one dword that the row's four c lanes all load, and the lane picks byte
+// c; otherwise the lane loads its own byte.
+template <bool SA>
+__device__ __forceinline__ uint32_t mx4_scale_load(const uint8_t* sr, int c) {
+  if constexpr (SA)
+    return *reinterpret_cast<const uint32_t*>(sr);
+  else
+    return (uint32_t)sr[c] << (8 * c);
 }
 
 }  // namespace mp

@@ -20,6 +20,11 @@
 // 4-bit weights with one f32 scale per 128 k of a row (int4g128: ops.quantize_w4) run the
 // sibling kernel gemv_w4_kernel below: the same plan, lanes and reduction, but a step is
 // exactly one group, so its MFMAs go into a tile of their own and acc += scale * tile in f32.
+//
+// MXFP4 weights (e2m1 values, one e8m0 scale byte per 32 k: ops.quant.quantize_mx4) run
+// gemv_mx4_kernel: again the same plan, lanes and reduction.  A lane's 32 k are exactly one MX
+// group, so its scale is folded into the conversion (v_cvt_scalef32_pk_bf16_fp4) and the MFMAs
+// of a step accumulate straight into acc, as in the int8 kernel.
 #include "mp_api.h"
 #include "mp_common.h"
 #include "mp_gemv_frags.h"
@@ -258,6 +263,133 @@ int launch_w4(const GemvArgs& a, const gemv::Plan& p, bool xa, hipStream_t st) {
   return launch_w4_g<1>(a, p, xa, st);
 }
 
+// ---- MXFP4 weights (e2m1, one e8m0 byte per 32 k): MX4Frag and mx4_scale_load of mp_gemv_frags.h ----
+
+// U steps from step s on: every load first (weights, the step's scale dword, x), then per step
+// and MFMA slot the conversion with the lane's scale folded in and the MFMAs straight into acc
+template <int G, bool XA, int U, bool SA>
+__device__ __forceinline__ void run_steps_mx4(f32x4 (&acc)[G], const uint8_t* const (&wrow)[G],
+                                              const uint8_t* const (&srow)[G], const bf16_t* xrow, bool xon, int s,
+                                              int c) {
+  MX4Frag wf[U][G];
+  uint32_t sc[U][G];
+  XFrag<XA> xf[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int64_t st = s + u;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      wf[u][g].load(wrow[g] + st * (gemv::KSTEP / 2));
+      sc[u][g] = mx4_scale_load<SA>(srow[g] + st * 4, c);
+    }
+    xf[u].load(xrow + st * gemv::KSTEP, xon);
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    float f[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) f[g] = mx4_scale((sc[u][g] >> (8 * c)) & 0xffu);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bf16x8 b = xf[u].frag(j);
+#pragma unroll
+      for (int g = 0; g < G; ++g)
+        acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[u][g].frag(j, f[g]), b, acc[g], 0, 0, 0);
+    }
+  }
+}
+
+template <int G, bool XA>
+__global__ __launch_bounds__(G == 1 ? 1024 : 512) void gemv_mx4_kernel(GemvArgs a) {
+  extern __shared__ f32x4 red[];      // [ksplit - 1][G][64]
+  // steps loaded ahead of their MFMAs: a step holds 16 VGPRs of x beside 5 G of packed weights
+  // and scale bytes; the 16 G of a step's converted operand live only around its MFMAs
+  constexpr int U = G == 4 ? 2 : 4;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, S = blockDim.x >> 6;
+  const int i = lane & 15, c = lane >> 4;
+  const int64_t n0 = (int64_t)blockIdx.x * (16 * G);
+  const int steps = a.K / gemv::KSTEP;          // K % 128 == 0: four whole MX groups per row and step
+  const int per = (steps + S - 1) / S;
+  const int b = wave * per, e = min(b + per, steps);
+
+  const uint8_t* wrow[G];
+  const uint8_t* srow[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    // rows past N re-read row N - 1 (in bounds), weights and scales; their results are never stored
+    const int64_t n = min(n0 + 16 * g + i, (int64_t)a.N - 1);
+    wrow[g] = reinterpret_cast<const uint8_t*>(a.w) + n * (a.K / 2) + 16 * c;
+    srow[g] = reinterpret_cast<const uint8_t*>(a.scale) + n * (a.K / 32);
+  }
+  const bool xon = i < a.M;
+  const bf16_t* xrow = a.x + (xon ? (int64_t)i * a.ldx : 0) + 32 * c;
+  const bool sa = ((uintptr_t)a.scale & 3) == 0;
+
+  f32x4 acc[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) acc[g] = (f32x4)(0.f);
+  int s = b;
+  if (sa) {
+    for (; s + U <= e; s += U) run_steps_mx4<G, XA, U, true>(acc, wrow, srow, xrow, xon, s, c);
+    for (; s < e; ++s) run_steps_mx4<G, XA, 1, true>(acc, wrow, srow, xrow, xon, s, c);
+  } else {
+    for (; s + U <= e; s += U) run_steps_mx4<G, XA, U, false>(acc, wrow, srow, xrow, xon, s, c);
+    for (; s < e; ++s) run_steps_mx4<G, XA, 1, false>(acc, wrow, srow, xrow, xon, s, c);
+  }
+
+  if (S > 1) {
+    if (wave > 0) {
+#pragma unroll
+      for (int g = 0; g < G; ++g) red[((wave - 1) * G + g) * 64 + lane] = acc[g];
+    }
+    __syncthreads();
+    if (wave > 0) return;
+    for (int w = 1; w < S; ++w)
+#pragma unroll
+      for (int g = 0; g < G; ++g) acc[g] += red[((w - 1) * G + g) * 64 + lane];
+  }
+
+  // lane: x row m = i, weight rows n0 + 16 g + 4 c + r
+  if (!xon) return;
+  const int m = i;
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t n = n0 + 16 * g + 4 * c + r;
+      if (n >= a.N) continue;
+      float v = acc[g][r];
+      if (a.bias) v += bf2f(a.bias[n]);
+      if (a.gelu) v = gelu_tanh(IO8<bf16_t>::get_round(v));
+      if (a.res) v += bf2f(a.res[(int64_t)m * a.ldr + n]);
+      a.y[(int64_t)m * a.ldy + n] = f2bf(v);
+    }
+}
+
+template <int G>
+int launch_mx4_g(const GemvArgs& a, const gemv::Plan& p, bool xa, hipStream_t st) {
+  const size_t lds = (size_t)(p.ksplit - 1) * G * 64 * sizeof(f32x4);
+  const dim3 grid((unsigned)p.grid), block(64 * p.ksplit);
+  if (xa)
+    gemv_mx4_kernel<G, true><<<grid, block, lds, st>>>(a);
+  else
+    gemv_mx4_kernel<G, false><<<grid, block, lds, st>>>(a);
+  return (int)hipGetLastError();
+}
+
+// out[n, k] = bf16(e2m1(nibble) * 2^(scale[n, k / 32] - 127)): one MX group (16 bytes of q, one
+// scale byte) per thread, so thread t's scale is byte t of the table.  The conversion is exact.
+__global__ __launch_bounds__(256) void dequant_mx4_kernel(const uint8_t* __restrict__ q, const uint8_t* __restrict__ scale,
+                                                          bf16_t* __restrict__ out, int64_t chunks) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= chunks) return;
+  MX4Frag f;
+  f.load(q + 16 * t);
+  const float sc = mx4_scale(scale[t]);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) *reinterpret_cast<bf16x8*>(out + 32 * t + 8 * j) = f.frag(j, sc);
+}
+
 // out[n, k] = bf16(q[n, k] * scale[n]); 16 elements per thread
 __global__ __launch_bounds__(256) void dequant_w8_kernel(const int8_t* __restrict__ q, const float* __restrict__ scale,
                                                          bf16_t* __restrict__ out, int64_t chunks, int chunks_per_row) {
@@ -333,5 +465,32 @@ extern "C" int mp_dequant_w4(const void* q, const float* scale, void* out, int64
   if ((chunks + 255) / 256 > 0x7fffffff || K / 32 > 0x7fffffff) return -1;
   mp::dequant_w4_kernel<<<dim3((unsigned)((chunks + 255) / 256)), 256, 0, st>>>(
       (const uint8_t*)q, scale, (mp::bf16_t*)out, chunks, (int)(K / 32), N);
+  return (int)hipGetLastError();
+}
+
+// MXFP4: w = packed e2m1 [N, K / 2], scale = e8m0 bytes [N, K / 32] (any alignment).  The plan is
+// the 4-bit one: the streamed bytes per row are int4g128's.  Returns as mp_gemv_skinny does.
+extern "C" int mp_gemv_mx4(const void* w, const uint8_t* scale, const void* x, void* y, const void* bias,
+                           const void* res, int M, int N, int K, int64_t ldx, int64_t ldy, int64_t ldr, int gelu,
+                           int force_split, hipStream_t st) {
+  const gemv::Plan p = gemv::plan(N, K, 0, force_split);
+  if (p.rows == 0 || M < 1 || M > gemv::MAX_M || scale == nullptr || ((uintptr_t)w & 15)) return -1;
+  mp::GemvArgs a;
+  a.w = w, a.scale = reinterpret_cast<const float*>(scale), a.x = (const mp::bf16_t*)x, a.y = (mp::bf16_t*)y;
+  a.bias = (const mp::bf16_t*)bias, a.res = (const mp::bf16_t*)res;
+  a.M = M, a.N = N, a.K = K, a.gelu = gelu, a.ldx = ldx, a.ldy = ldy, a.ldr = ldr;
+  const bool xa = ((uintptr_t)x & 15) == 0 && (M == 1 || ldx % 8 == 0);
+  if (p.rows == 64) return mp::launch_mx4_g<4>(a, p, xa, st);
+  if (p.rows == 32) return mp::launch_mx4_g<2>(a, p, xa, st);
+  return mp::launch_mx4_g<1>(a, p, xa, st);
+}
+
+// q [N, K / 2] packed e2m1, scale [N, K / 32] e8m0 bytes, out bf16 [N, K]
+extern "C" int mp_dequant_mx4(const void* q, const uint8_t* scale, void* out, int64_t N, int64_t K, hipStream_t st) {
+  if (N < 1 || K < 128 || K % 128 != 0 || ((uintptr_t)q & 15) || ((uintptr_t)out & 15)) return -1;
+  const int64_t chunks = N * (K / 32);
+  if ((chunks + 255) / 256 > 0x7fffffff) return -1;
+  mp::dequant_mx4_kernel<<<dim3((unsigned)((chunks + 255) / 256)), 256, 0, st>>>((const uint8_t*)q, scale,
+                                                                                 (mp::bf16_t*)out, chunks);
   return (int)hipGetLastError();
 }

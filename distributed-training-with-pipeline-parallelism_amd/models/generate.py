@@ -139,6 +139,8 @@ class KVCache:
 
 QUANTIZED = ("attn.wqkv.weight", "attn.wo.weight", "ffn.w1.weight", "ffn.w2.weight", "ffn.w13.weight")
 QUANT_FORMATS = tuple(ops.QUANT_FORMATS)
+# every name ``weights=`` / ``fmt=`` takes besides "bf16": the table above and the MX formats (mxfp4)
+WEIGHT_FORMATS = QUANT_FORMATS + tuple(ops.quant.MX_FORMATS)
 
 
 def model_param_specs(cfg: NativeConfig) -> List[ParamSpec]:
@@ -172,11 +174,13 @@ class QuantWeights:
 
     ``fmt="int4g128"``: ``q[name]`` is packed uint8 [N, K / 2] and ``scale[name]`` f32
     [K / 128, N], the format of :func:`ops.quantize_w4`; every quantised matrix needs
-    ``K % 128 == 0`` (checked here, before anything is stored)."""
+    ``K % 128 == 0`` (checked here, before anything is stored).  ``fmt="mxfp4"``: packed e2m1
+    uint8 [N, K / 2] and e8m0 scale bytes uint8 [N, K / 32], the format of
+    :func:`ops.quant.quantize_mx4`, with the same ``K % 128 == 0``."""
 
     def __init__(self, cfg: NativeConfig, device, dtype=torch.bfloat16, fmt: str = "int8"):
-        if fmt not in QUANT_FORMATS:
-            raise ValueError(f"QuantWeights: format must be one of {QUANT_FORMATS}, got {fmt!r}")
+        if fmt not in WEIGHT_FORMATS:
+            raise ValueError(f"QuantWeights: format must be one of {WEIGHT_FORMATS}, got {fmt!r}")
         self.fmt = fmt
         self.cfg = cfg
         self.device = torch.device(device)
@@ -188,7 +192,7 @@ class QuantWeights:
         self.q: Dict[str, torch.Tensor] = {}
         self.scale: Dict[str, torch.Tensor] = {}
         self.dense: Dict[str, torch.Tensor] = {}
-        mult = ops.QUANT_FORMATS[fmt].k_format
+        mult = ops.quant.quant_format(fmt).k_format
         bad = [(n, self.specs[n].shape) for n in self.order if self.quantized(n) and self.specs[n].shape[1] % mult != 0]
         if bad:
             raise ValueError(f"QuantWeights: {fmt} needs K % {mult} == 0 in every quantised matrix; "
@@ -212,7 +216,7 @@ class QuantWeights:
         s = self.specs[name]
         t = t.detach().float().reshape(s.shape)
         if self.quantized(name):
-            q, scale = ops.QUANT_FORMATS[self.fmt].quantize(t)
+            q, scale = ops.quant.quant_format(self.fmt).quantize(t)
             self.q[name], self.scale[name] = q.to(self.device), scale.to(self.device)
         # dense: everything but the block matrices and an untied head (a tied head is also
         # the embedding table, which stays dense)
@@ -241,7 +245,7 @@ class QuantWeights:
             self.put(n, sd[n])
 
     def _what(self, n: str) -> torch.Tensor:
-        return ops.QUANT_FORMATS[self.fmt].dequant(self.q[n].cpu(), self.scale[n].cpu())
+        return ops.quant.quant_format(self.fmt).dequant(self.q[n].cpu(), self.scale[n].cpu())
 
     def effective_state_dict(self) -> Dict[str, torch.Tensor]:
         """f32 CPU tensors by FQN of the weights this generator computes with: ``q * scale``
@@ -281,8 +285,8 @@ class _QBlock:
 
 
 def _check_weights(weights: str, skinny: bool) -> None:
-    if weights != "bf16" and weights not in QUANT_FORMATS:
-        raise ValueError(f"Generator: weights must be 'bf16', 'int8' or 'int4g128', got {weights!r}")
+    if weights != "bf16" and weights not in WEIGHT_FORMATS:
+        raise ValueError(f"Generator: weights must be 'bf16', 'int8', 'int4g128' or 'mxfp4', got {weights!r}")
     if skinny and weights != "bf16":
         raise ValueError("Generator: skinny=True is the bf16 weights' opt-in (quantised weights always use the skinny "
                          "kernel)")
@@ -299,7 +303,10 @@ class Generator:
     dequantise into one scratch matrix, allocated on the first call that needs it.  GELU /
     SwiGLU models only.  ``weights="int4g128"``: the same with 4-bit values and one scale per
     128-element group of K (:func:`ops.quantize_w4`, :func:`ops.linear_w4`); every quantised
-    matrix then needs ``K % 128 == 0``.  ``skinny=True`` (bf16 weights on the GPU only): linear layers of at
+    matrix then needs ``K % 128 == 0``.  ``weights="mxfp4"``: OCP MXFP4 (e2m1 values, one
+    power-of-two scale per 32 k: :func:`ops.quant.quantize_mx4`, :func:`ops.quant.linear_mx4`), the
+    same in every other respect; with ``skinny64=True`` its layers of more than 16 rows still
+    dequantise.  ``skinny=True`` (bf16 weights on the GPU only): linear layers of at
     most 16 rows run the bf16 instantiation of the same kernel instead of the training GEMM.
 
     ``skinny64=True`` (off by default): linear layers of 17 to 64 rows -- a batched decode, the

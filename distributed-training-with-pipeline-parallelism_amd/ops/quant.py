@@ -1,6 +1,7 @@
 """Weight-only quantised linear layers on the skinny-M kernel (csrc/kernels/gemv_skinny.hip,
 csrc/bindings/quant.cpp).  The formats differ in a handful of functions and numbers, held in
-``QUANT_FORMATS``; the skinny call and the any-M linear are one code path over that table."""
+``QUANT_FORMATS`` and ``MX_FORMATS`` (found by :func:`quant_format`); the skinny call and the any-M
+linear are one code path over those tables."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -147,6 +148,89 @@ def dequant_w4(q4: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor
     return out
 
 
+# mxfp4: OCP MXFP4 -- e2m1 elements with one e8m0 (power-of-two) scale per 32 k -- on gemv_mx4_kernel.  Names of
+# this module only
+MX_GROUP = 32
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_mx4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """OCP MXFP4 quantisation of a 2-D weight ``w [N, K]`` (bf16 or f32, ``K % 128 == 0``, else
+    ValueError) -> ``(q4, scale)``, all arithmetic in f32, per group of 32 k:
+
+    * ``scale`` uint8 ``[N, K / 32]``: byte ``e`` stands for ``2^(e - 127)`` (e8m0).  With ``amax``
+      the group's largest magnitude, ``E = floor(log2(amax)) - 2`` (from ``torch.frexp``; 2 is
+      the exponent of e2m1's largest value, 6) clamped to [-127, 127] and the byte is
+      ``E + 127``.  A group of zeros gets byte 0 and codes 0; byte 255 (NaN) is never written.
+    * each element is ``w / 2^E`` rounded to the nearest e2m1 magnitude (0, 0.5, 1, 1.5, 2, 3,
+      4, 6), ties to the even code, above 6 to 6.  A code is sign << 3 | index of the magnitude;
+      a value that rounds to 0 gets code 0 (code 8, -0, is never written; consumers read it as 0).
+    * ``q4`` uint8 ``[N, K / 2]``: byte ``b`` of a row holds element ``2 b`` in its low nibble and
+      ``2 b + 1`` in its high one (the order of ``torch.float4_e2m1fn_x2``).
+
+    The effective weight is ``What[n, k] = e2m1(code[n, k]) * 2^(scale[n, k // 32] - 127)``.
+    Pure tensor code, the same values on every device."""
+    if w.dim() != 2:
+        raise ValueError("quantize_mx4: w must be [N, K]")
+    N, K = w.shape
+    if K < W4_GROUP or K % W4_GROUP != 0:
+        raise ValueError(f"quantize_mx4: K = {K} must be a multiple of {W4_GROUP}")
+    wf = w.detach().float().reshape(N, K // MX_GROUP, MX_GROUP)
+    amax = wf.abs().amax(dim=2)
+    E = (torch.frexp(amax)[1].to(torch.int32) - 3).clamp_(-127, 127)       # amax = m 2^ex, m in [0.5, 1)
+    E = torch.where(amax > 0, E, torch.full_like(E, -127))
+    # 2^-E built from its bits (E <= 125 for any finite f32 amax, so the exponent field stays in
+    # [2, 254]): an exact power of two on every device, and so is the product
+    a = (wf * ((127 - E) << 23).view(torch.float32)[:, :, None]).abs()
+    # the seven midpoints between neighbouring magnitudes; a tie goes to the even code, so the
+    # midpoints below an even code are included (>=) and those above one are not (>)
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0))
+    code = (code | (((wf < 0) & (code > 0)).to(torch.uint8) << 3)).reshape(N, K)
+    return (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous(), (E + 127).to(torch.uint8).contiguous()
+
+
+def _mx4_check(name, x, q4, scale):
+    if q4.dtype != torch.uint8 or q4.dim() != 2 or x.dim() != 2 or x.shape[1] != 2 * q4.shape[1]:
+        raise ValueError(f"{name}: x [M, K] and packed uint8 q4 [N, K / 2] needed, got {tuple(x.shape)} and "
+                         f"{q4.dtype} {tuple(q4.shape)}")
+    N, K = q4.shape[0], 2 * q4.shape[1]
+    if K % W4_GROUP != 0:
+        raise ValueError(f"{name}: K = {K} must be a multiple of {W4_GROUP}")
+    if scale is None or scale.dtype != torch.uint8 or tuple(scale.shape) != (N, K // MX_GROUP):
+        raise ValueError(f"{name}: scale must be uint8 [N, K / 32] = [{N}, {K // MX_GROUP}]")
+
+
+def _mx4_what(q4, scale):
+    """f32 [N, K]: e2m1(code) * 2^(byte - 127), exact (2^-127 is an f32 subnormal; byte 255 is NaN)"""
+    lut = torch.tensor(_E2M1 + (0.0,) + tuple(-v for v in _E2M1[1:]), device=q4.device)
+    e8 = torch.tensor([2.0 ** (e - 127) for e in range(255)] + [float("nan")], device=q4.device)
+    b = q4.to(torch.int64)
+    val = lut[torch.stack((b & 15, b >> 4), dim=2).reshape(q4.shape[0], -1)]
+    return val * e8[scale.to(torch.int64)].repeat_interleave(MX_GROUP, dim=1)
+
+
+def _mx4_matmul_cpu(x, q4, scale):
+    return x.float() @ _mx4_what(q4, scale).t()
+
+
+def dequant_mx4(q4: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [N, K] = the effective weight of :func:`quantize_mx4`'s format in out's dtype (bf16 on
+    the GPU, where one v_cvt_scalef32_pk_bf16_fp4 makes two elements).  Exact while the value
+    is a normal bf16 (scale bytes in [2, 250]); a zero may carry code 8's sign."""
+    N, K = q4.shape[0], 2 * q4.shape[1]
+    if q4.dtype != torch.uint8 or K % W4_GROUP != 0 or scale.dtype != torch.uint8 or \
+            tuple(scale.shape) != (N, K // MX_GROUP):
+        raise ValueError(f"dequant_mx4: packed uint8 q4 [N, K / 2] with K % 128 == 0 and uint8 scale [N, K / 32] needed, "
+                         f"got {q4.dtype} {tuple(q4.shape)} and {scale.dtype} {tuple(scale.shape)}")
+    if out is None:
+        out = torch.empty(N, K, device=q4.device, dtype=torch.bfloat16 if _gpu(q4) else torch.float32)
+    if _gpu(q4):
+        _ext().dequant_w8(q4, scale, out)
+    else:
+        out.copy_(_mx4_what(q4, scale).to(out.dtype))
+    return out
+
+
 # One entry per format, holding what differs: the operand check (name, x, q, scale); x @ What^T in f32 on the CPU,
 # scaled in the kernel's order; quantize and dequant; the K multiple a matrix needs to be stored (k_format) and to be
 # read by the skinny kernel (k_skinny); the names its errors carry and where the skinny kernel's M bound points
@@ -157,6 +241,16 @@ QUANT_FORMATS = {
     "int4g128": _Format(_w4_check, _w4_matmul_cpu, quantize_w4, dequant_w4, W4_GROUP, W4_GROUP,
                         "linear_skinny_w4", "linear_w4", "linear_w4 takes any M"),
 }
+# the formats of power-of-two block scales; ``QUANT_FORMATS`` keeps its two entries
+MX_FORMATS = {
+    "mxfp4": _Format(_mx4_check, _mx4_matmul_cpu, quantize_mx4, dequant_mx4, W4_GROUP, W4_GROUP,
+                     "linear_skinny_mx4", "linear_mx4", "linear_mx4 takes any M"),
+}
+
+
+def quant_format(fmt: str) -> _Format:
+    """The record of a format of either table by its name (KeyError otherwise)."""
+    return QUANT_FORMATS[fmt] if fmt in QUANT_FORMATS else MX_FORMATS[fmt]
 
 
 def _checked(name, f, x, q, scale, bias, act, residual, out):
@@ -207,25 +301,28 @@ def reads_weights_directly(x: torch.Tensor, fmt: str, rows64: bool = False) -> b
     skinny kernel, or with ``rows64`` its 64-row sibling) and so needs no scratch.  The one
     statement of that route: ``linear_q`` and the generator both ask here."""
     M, K = x.shape
-    if K % QUANT_FORMATS[fmt].k_skinny != 0:
+    if K % quant_format(fmt).k_skinny != 0:
         return False
+    # the 64-row sibling has no MXFP4 instantiation: those layers dequantise above 16 rows
+    rows64 = rows64 and fmt not in MX_FORMATS
     return M <= W8_SKINNY_MAX_M or (rows64 and M <= SKINNY64_MAX_M and _x_aligned(x))
 
 
 def linear_q(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, fmt: str, bias: Optional[torch.Tensor] = None,
              act: str = "none", residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
              scratch: Optional[torch.Tensor] = None, rows64: bool = False) -> torch.Tensor:
-    """:func:`linear_w8` / :func:`linear_w4` by the name of the format, a key of ``QUANT_FORMATS``.
+    """:func:`linear_w8` / :func:`linear_w4` / :func:`linear_mx4` by the name of the format, a key of
+    ``QUANT_FORMATS`` or ``MX_FORMATS``.
     ``rows64=True``: on the GPU, ``W8_SKINNY_MAX_M < M <= SKINNY64_MAX_M`` rows (16-byte aligned,
     ``K`` a multiple of the format's skinny step) run :func:`linear_skinny64` on the quantised
     matrix itself instead of dequantising: no scratch is touched."""
-    f = QUANT_FORMATS[fmt]
+    f = quant_format(fmt)
     M, N, K, out = _checked(f.linear, f, x, q, scale, bias, act, residual, out)
     if not _gpu(x):
         return _linear_cpu(f, x, q, scale, bias, act, residual, out)
     if reads_weights_directly(x, fmt, rows64):
         return _skinny(f, x, q, scale, bias, act, residual, out, 0, checked=(M, N, K, out),
-                       max_m=SKINNY64_MAX_M if rows64 else SKINNY_MAX_M)
+                       max_m=SKINNY64_MAX_M if rows64 and fmt not in MX_FORMATS else SKINNY_MAX_M)
     if scratch is None:
         scratch = torch.empty(N * K, device=x.device, dtype=torch.bfloat16)
     if scratch.dtype != torch.bfloat16 or scratch.numel() < N * K or not scratch.is_contiguous():
@@ -290,3 +387,22 @@ def linear_w4(x: torch.Tensor, q4: torch.Tensor, scale: torch.Tensor, bias: Opti
     written as bf16 into ``scratch`` (at least N * K elements; allocated here if None) and
     the training GEMM runs on that.  Returns y."""
     return linear_q(x, q4, scale, "int4g128", bias, act, residual, out, scratch)
+
+
+def linear_skinny_mx4(x: torch.Tensor, q4: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                      act: str = "none", residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                      force_split: int = 0) -> torch.Tensor:
+    """:func:`linear_skinny` over MXFP4 weights (:func:`quantize_mx4`): ``q4`` uint8 [N, K / 2],
+    ``scale`` uint8 [N, K / 32] (any alignment), at most 16 rows of x.  The kernel converts
+    codes and scale to the bf16 effective weight in one instruction and accumulates
+    ``x @ What^T`` in f32.  Everything else is as in :func:`linear_skinny`.  Returns y."""
+    return _skinny(MX_FORMATS["mxfp4"], x, q4, scale, bias, act, residual, out, force_split)
+
+
+def linear_mx4(x: torch.Tensor, q4: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
+               act: str = "none", residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+               scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`linear` over MXFP4 weights, any number of rows: the skinny kernel on ``q4`` itself
+    up to ``W8_SKINNY_MAX_M`` rows, :func:`dequant_mx4` into ``scratch`` and the training GEMM
+    above (there is no 64-row kernel for this format).  Returns y."""
+    return linear_q(x, q4, scale, "mxfp4", bias, act, residual, out, scratch)

@@ -29,7 +29,8 @@ the acceptance rate goes to stderr.
 ``--weights int8`` quantises the block matrices and the LM head per output row while loading
 (int8 weight-only inference; the draft of ``--draft-checkpoint`` follows ``--draft-weights``).
 ``--weights int4g128`` stores them as 4-bit values with one scale per 128-element group of K
-instead (every such matrix needs K % 128 == 0).
+instead (every such matrix needs K % 128 == 0); ``--weights mxfp4`` as OCP MXFP4 (e2m1 values
+with one power-of-two scale per 32 elements of K, the same K % 128 == 0).
 
 ``--skinny64`` runs linear layers of 17 to 64 rows (a batch of up to 64 prompts, the verifying
 pass of speculative decoding, a short prefill) on the 64-row weight-streaming kernel, with any
@@ -67,10 +68,10 @@ def main(argv=None) -> int:
                     "draft model (same vocabulary; greedy only)")
     ap.add_argument("--lookahead", type=int, default=4, help="tokens the draft proposes per round")
     ap.add_argument("--device", choices=("cpu", "cuda"), default=None, help="default: cuda when available")
-    ap.add_argument("--weights", choices=("bf16", "int8", "int4g128"), default="bf16",
+    ap.add_argument("--weights", choices=("bf16", "int8", "int4g128", "mxfp4"), default="bf16",
                     help="int8 / int4g128: weight-only quantisation of the block matrices and the LM head at load "
                     "(per output row / 4-bit with one scale per 128 k)")
-    ap.add_argument("--draft-weights", choices=("bf16", "int8", "int4g128"), default="bf16",
+    ap.add_argument("--draft-weights", choices=("bf16", "int8", "int4g128", "mxfp4"), default="bf16",
                     help="the same for the draft model")
     ap.add_argument("--kv-cache", choices=("bf16", "int8"), default="bf16",
                     help="int8: K / V cache rows as int8 with one f32 scale per (token, KV head)")

@@ -1,6 +1,6 @@
-"""Time of the skinny-M kernel (int8, int4g128 and bf16 weights) against ``ops.linear`` per GEMM
-shape, and end-to-end tokens/s of bf16, bf16 ``skinny=True``, int8 and int4g128 generators, on
-one GPU.
+"""Time of the skinny-M kernel (int8, int4g128, mxfp4 and bf16 weights) against ``ops.linear`` per
+GEMM shape, and end-to-end tokens/s of bf16, bf16 ``skinny=True``, int8, int4g128 and mxfp4
+generators, on one GPU.
 
     python tools/w8_time.py                       # both tables (profiles/r12_w8_decode.md, r13_w4_decode.md)
     python tools/w8_time.py --parts gemm --models llama3-1b --rows 1,16
@@ -17,7 +17,8 @@ events.  Each call takes the next of several copies of the weight (together at l
 than from the 256 MB Infinity Cache, as it does inside a decode step of a model that does not
 fit there; ``copies`` is printed.  Variants: ``w8`` = ops.linear_w8 (the skinny kernel up to
 W8_SKINNY_MAX_M rows, dequantise + ops.linear above), ``w4`` = ops.linear_w4 on the int4g128
-format of the same weights (the same routes), ``skinny_bf16`` (up to 16 rows),
+format of the same weights (the same routes), ``mx4`` = ops.quant.linear_mx4 on their MXFP4 format
+(profiles/r16_mx4_decode.md), ``skinny_bf16`` (up to 16 rows),
 ``linear`` = ops.linear on bf16 weights, ``dequant_linear`` = dequant_w8 + ops.linear at every
 M (the crossover).  Above 16 and up to 64 rows four more alternate in the same windows:
 ``rows64`` / ``rows64_w4`` / ``rows64_bf16`` = ops.quant.linear_skinny64 on the int8 / int4g128 /
@@ -26,7 +27,7 @@ on the int8 weights, which reads and converts them that many times.  Every recor
 ``<variant>_spread_us``, the largest minus the smallest window.  MIPIPE_EXT_VARIANT=xreg (a
 ``tools/build_ext.py --variant xreg -DMP_ROWS64_XREG`` build) times the register-direct x path
 of the 64-row kernel in a process of its own.  GB/s counts the weight bytes of the variant's
-own format once per call (for ``w4`` the packed nibbles and their group scales: N K / 2 +
+own format once per call (for ``w4`` and ``mx4`` the packed nibbles and their scales: N K / 2 +
 N K / 32 bytes).
 
 End to end (``--parts e2e``): greedy ``generate_batch`` (eager step) of one set of weights as
@@ -99,6 +100,7 @@ def gemm_part(a, dev):
             w = [torch.randn(N, K, device=dev, dtype=torch.bfloat16) * (K ** -0.5) for _ in range(copies)]
             qs = [ops.quantize_w8(t) for t in w]
             q4s = [ops.quantize_w4(t) for t in w]
+            mxs = [ops.quant.quantize_mx4(t) for t in w]
             scratch = torch.empty(N * K, device=dev, dtype=torch.bfloat16)
             for M in (int(m) for m in a.rows.split(",")):
                 x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
@@ -106,6 +108,7 @@ def gemm_part(a, dev):
                 variants = {
                     "w8": lambda i: ops.linear_w8(x, *qs[i % copies], out=y, scratch=scratch),
                     "w4": lambda i: ops.linear_w4(x, *q4s[i % copies], out=y, scratch=scratch),
+                    "mx4": lambda i: ops.quant.linear_mx4(x, *mxs[i % copies], out=y, scratch=scratch),
                     "linear": lambda i: ops.linear(x, w[i % copies], out=y),
                     "dequant_linear": lambda i: ops.linear(
                         x, ops.dequant_w8(*qs[i % copies], scratch.view(N, K)), out=y),
@@ -123,14 +126,14 @@ def gemm_part(a, dev):
                 rec = {"model": mname, "layer": lname, "N": N, "K": K, "M": M, "copies": copies,
                        "w8_route": "skinny" if M <= ops.W8_SKINNY_MAX_M else "dequant"}
                 for name, sec in t.items():
-                    wbytes = N * K // 2 + N * K // 32 if name in ("w4", "rows64_w4") else \
+                    wbytes = N * K // 2 + N * K // 32 if name in ("w4", "mx4", "rows64_w4") else \
                         N * K * (1 if name in ("w8", "dequant_linear", "rows64", "loop") else 2)
                     rec[f"{name}_us"] = round(sec * 1e6, 1)
                     rec[f"{name}_spread_us"] = round(spread[name] * 1e6, 1)
                     rec[f"{name}_gbs"] = round(wbytes / sec * 1e-9)
                 print(json.dumps(rec), flush=True)
                 recs.append(rec)
-            del w, qs, q4s, scratch
+            del w, qs, q4s, mxs, scratch
             torch.cuda.empty_cache()
     return recs
 
@@ -144,6 +147,7 @@ def e2e_part(a, dev):
         gens = {"bf16": base, "bf16_skinny": mipipe.Generator.from_model(base.model, skinny=True),
                 "int8": mipipe.Generator.from_model(base.model, weights="int8"),
                 "int4g128": mipipe.Generator.from_model(base.model, weights="int4g128"),
+                "mxfp4": mipipe.Generator.from_model(base.model, weights="mxfp4"),
                 "bf16_skinny64": mipipe.Generator.from_model(base.model, skinny64=True),
                 "int8_skinny64": mipipe.Generator.from_model(base.model, weights="int8", skinny64=True)}
         for B in (int(b) for b in a.batches.split(",")):
@@ -171,6 +175,8 @@ def e2e_part(a, dev):
             rec["int8_vs_bf16"] = round(rec["int8_tok_s"] / rec["bf16_tok_s"], 3)
             rec["int4g128_vs_bf16"] = round(rec["int4g128_tok_s"] / rec["bf16_tok_s"], 3)
             rec["int4g128_vs_int8"] = round(rec["int4g128_tok_s"] / rec["int8_tok_s"], 3)
+            rec["mxfp4_vs_int4g128"] = round(rec["mxfp4_tok_s"] / rec["int4g128_tok_s"], 3)
+            rec["mxfp4_vs_int8"] = round(rec["mxfp4_tok_s"] / rec["int8_tok_s"], 3)
             rec["int8_skinny64_vs_int8"] = round(rec["int8_skinny64_tok_s"] / rec["int8_tok_s"], 3)
             rec["int8_skinny64_vs_bf16"] = round(rec["int8_skinny64_tok_s"] / rec["bf16_tok_s"], 3)
             for n in variants:
@@ -191,12 +197,13 @@ def e2e_part(a, dev):
 
 def _markdown(gemm, e2e):
     if gemm:
-        print("\n| model | layer | N x K | M | w4 us | w4 GB/s | w8 us | w8 GB/s | skinny bf16 us | GB/s | linear us | GB/s "
+        print("\n| model | layer | N x K | M | mx4 us | mx4 GB/s | w4 us | w4 GB/s | w8 us | w8 GB/s | skinny bf16 us | GB/s | linear us | GB/s "
               "| dequant+linear us | rows64 us | rows64 w4 us | rows64 bf16 us | loop us |")
-        print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+        print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
         for r in gemm:
             sk = (r.get("skinny_bf16_us", "-"), r.get("skinny_bf16_gbs", "-"))
-            print(f"| {r['model']} | {r['layer']} | {r['N']} x {r['K']} | {r['M']} | {r['w4_us']} | {r['w4_gbs']} | "
+            print(f"| {r['model']} | {r['layer']} | {r['N']} x {r['K']} | {r['M']} | {r['mx4_us']} | {r['mx4_gbs']} | {r['w4_us']} | "
+                  f"{r['w4_gbs']} | "
                   f"{r['w8_us']} ({r['w8_route']}) | "
                   f"{r['w8_gbs']} | {sk[0]} | {sk[1]} | {r['linear_us']} | {r['linear_gbs']} | {r['dequant_linear_us']} | "
                   + " | ".join(str(r.get(f"{n}_us", "-")) for n in ("rows64", "rows64_w4", "rows64_bf16", "loop")) + " |")
