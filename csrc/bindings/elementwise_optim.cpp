@@ -59,7 +59,23 @@ void adamw(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c
         "adamw");
 }
 
+// dst float8_e4m3fn: the quantising cast to MXFP8 rows (mx8_quantize_rows_kernel of gemm_mx.hip).  src: bf16 or f32
+// rows [M, K] of any stride, K % 128 == 0; dst: contiguous [M, round_up(K + K / 32, 16)], 16-byte aligned
 void cast_f32_bf16(torch::Tensor src, torch::Tensor dst) {
+  if (dst.scalar_type() == torch::kFloat8_e4m3fn) {
+    const int f32 = storage(src, "cast (MXFP8): src");
+    TORCH_CHECK(src.is_cuda() && src.dim() == 2 && src.stride(1) == 1 && src.size(0) >= 1 &&
+                    (src.size(0) == 1 || src.stride(0) >= src.size(1)), "cast (MXFP8): src must be GPU rows [M, K]");
+    const int64_t M = src.size(0), K = src.size(1);
+    TORCH_CHECK(K >= 128 && K % 128 == 0 && K <= 1 << 24, "cast (MXFP8): K = ", K, " must be a multiple of 128");
+    req(dst, torch::kFloat8_e4m3fn, "cast (MXFP8): dst");
+    TORCH_CHECK(dst.dim() == 2 && dst.size(0) == M && dst.size(1) == (K + K / 32 + 15) / 16 * 16 && aligned16(dst) &&
+                    dst.get_device() == src.get_device(),
+                "cast (MXFP8): dst must be 16-byte aligned [M, round_up(K + K / 32, 16)] on src's GPU");
+    check(mp_mx8_quantize_rows(src.data_ptr(), f32, src.stride(0), dst.data_ptr(), M, (int)K, cur_stream()),
+          "cast (MXFP8)");
+    return;
+  }
   req(src, torch::kFloat32, "src");
   reqn(dst, torch::kBFloat16, src.numel(), "dst");
   check(mp_cast_f32_bf16(src.data_ptr<float>(), dst.data_ptr(), src.numel(), cur_stream()), "cast");

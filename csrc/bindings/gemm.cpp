@@ -2,6 +2,7 @@
 // the transposes beside them (elementwise.hip) and the skinny-M GEMV (gemv_skinny.hip).
 #include "common.h"
 #include "mp_gemm_plan.h"
+#include "mp_gemm_mx_plan.h"
 #include "mp_gemv_plan.h"
 
 namespace mipipe_bind {
@@ -220,7 +221,8 @@ void transpose_batched(torch::Tensor src, torch::Tensor dst, torch::Tensor desc,
 // y[M, N] = epi(x[M, K] @ What^T), M <= 16 (csrc/kernels/gemv_skinny.hip) or 17 <= M <= 64 (gemv_rows64.hip: the
 // same rows bit for bit): w int8 [N, K] with scale f32 [N], w uint8 [N, K / 2] (packed 4-bit) with scale f32
 // [K / 128, N] (int4g128) or scale uint8 [N, K / 32] (MXFP4: e8m0 bytes; M <= 16), or w bf16 [N, K] without.
-// No allocation, no synchronisation.
+// x float8_e4m3fn [M, mx8_row_bytes(K)]: MXFP8 activation rows against MXFP4 weights on the scaled MFMA
+// (csrc/kernels/gemm_mx.hip), any M >= 1, force_split 0.  No allocation, no synchronisation.
 void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> scale, torch::Tensor y,
                  c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, bool gelu,
                  int64_t force_split) {
@@ -230,6 +232,42 @@ void gemv_skinny(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> 
                     (t.size(0) == 1 || t.stride(0) >= t.size(1)),
                 name, " must be bf16 GPU rows [M, cols] with a unit inner stride");
   };
+  if (x.scalar_type() == torch::kFloat8_e4m3fn) {
+    const char* fn = "gemv_skinny (MXFP8 x MXFP4)";
+    rows(y, "gemv_skinny: y");
+    TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous() && w.scalar_type() == torch::kUInt8 && aligned16(w) &&
+                    scale.has_value(), fn, ": w must be contiguous 16-byte aligned uint8 [N, K / 2] with a scale");
+    TORCH_CHECK(x.is_cuda() && x.dim() == 2, fn, ": x must be float8_e4m3fn GPU rows [M, round_up(K + K / 32, 16)]");
+    const int64_t M = x.size(0), N = w.size(0), K = 2 * w.size(1);
+    TORCH_CHECK(gemm_mx::plan(M, N, K).tile != gemm_mx::NONE, fn, ": M = ", M, ", N = ", N, ", K = ", K,
+                " is not supported (K a multiple of 128)");
+    TORCH_CHECK(x.stride(1) == 1 && x.size(1) == gemm_mx::mx8_row_bytes(K) && aligned16(x) &&
+                    (M == 1 || (x.stride(0) % 16 == 0 && x.stride(0) >= x.size(1))),
+                fn, ": x must be 16-byte aligned float8_e4m3fn GPU rows [M, round_up(K + K / 32, 16)]");
+    req(*scale, torch::kUInt8, "gemv_skinny: scale");
+    TORCH_CHECK(scale->dim() == 2 && scale->size(0) == N && scale->size(1) == K / 32,
+                fn, ": the scale of MXFP4 weights must be contiguous uint8 [N, K / 32]");
+    TORCH_CHECK(force_split == 0, fn, ": force_split must be 0 (K is never split)");
+    TORCH_CHECK(y.size(0) == M && y.size(1) == N, fn, ": y must be [M, N]");
+    if (bias.has_value()) {
+      req(*bias, torch::kBFloat16, "gemv_skinny: bias");
+      TORCH_CHECK(bias->numel() == N, "gemv_skinny: bias must hold N contiguous values");
+    }
+    TORCH_CHECK(!gelu || (bias.has_value() && !residual.has_value()), fn, ": the GELU epilogue needs a bias and no residual");
+    int64_t ldr = 0;
+    if (residual.has_value()) {
+      rows(*residual, "gemv_skinny: residual");
+      TORCH_CHECK(residual->size(0) == M && residual->size(1) == N, "gemv_skinny: residual must be [M, N]");
+      ldr = residual->stride(0);
+    }
+    for (const torch::Tensor* t : {&w, &*scale, &y, bias.has_value() ? &*bias : &y, residual.has_value() ? &*residual : &y})
+      TORCH_CHECK(t->get_device() == x.get_device(), fn, ": every tensor must be on x's GPU");
+    check(mp_gemm_mx(x.data_ptr(), w.data_ptr(), scale->data_ptr<uint8_t>(), y.data_ptr(), ptr_or_null(bias),
+                     ptr_or_null(residual), (int)M, (int)N, (int)K, x.stride(0), y.stride(0), ldr, gelu ? 1 : 0,
+                     cur_stream()),
+          fn);
+    return;
+  }
   rows(x, "gemv_skinny: x");
   rows(y, "gemv_skinny: y");
   TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous(), "gemv_skinny: w must be a contiguous [N, K] GPU matrix");

@@ -82,6 +82,12 @@ int mp_dequant_mx4(const void* q, const uint8_t* scale, void* out, int64_t N, in
 int mp_gemv_rows64(const void* w, const float* scale, int wbytes, const void* x, void* y, const void* bias,
                    const void* res, int M, int N, int K, int64_t ldx, int64_t ldy, int64_t ldr, int gelu,
                    int force_split, hipStream_t st);
+// ---- gemm_mx.hip.  MXFP8 activation rows (K e4m3 codes, K / 32 e8m0 bytes, zeros to a multiple of 16
+// bytes) times MXFP4 weights on the scaled MFMA, any M; and the quantiser that writes such rows from
+// bf16 (f32 != 0: f32) rows ldx elements apart.  Both return -1 for a shape or alignment they do not take.
+int mp_gemm_mx(const void* x, const void* w, const uint8_t* scale, void* y, const void* bias, const void* res, int M,
+               int N, int K, int64_t ldx, int64_t ldy, int64_t ldr, int gelu, hipStream_t st);
+int mp_mx8_quantize_rows(const void* x, int f32, int64_t ldx, void* out, int64_t M, int K, hipStream_t st);
 // ---- gemm_f32.hip.  a_kc / b_kc / b_nc: which stride of the operand is 1 (K- or N-contiguous);
 // both GEMMs return -1 for a layout they do not provide.
 int mp_gemm_f32(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int64_t lda,

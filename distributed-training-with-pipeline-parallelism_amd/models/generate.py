@@ -284,7 +284,11 @@ class _QBlock:
         return self.A.w(self.P + n) if self.A.has(self.P + n) else None
 
 
-def _check_weights(weights: str, skinny: bool) -> None:
+def _check_weights(weights: str, skinny: bool, activations: str = "bf16") -> None:
+    if activations not in ("bf16", "mxfp8"):
+        raise ValueError(f"Generator: activations must be 'bf16' or 'mxfp8', got {activations!r}")
+    if activations == "mxfp8" and weights != "mxfp4":
+        raise ValueError(f"Generator: activations='mxfp8' multiplies MXFP4 weights (weights='mxfp4'), got {weights!r}")
     if weights != "bf16" and weights not in WEIGHT_FORMATS:
         raise ValueError(f"Generator: weights must be 'bf16', 'int8', 'int4g128' or 'mxfp4', got {weights!r}")
     if skinny and weights != "bf16":
@@ -315,13 +319,20 @@ class Generator:
     kernel's.  Quantised generators then need no dequantisation scratch up to 64 rows; on bf16
     weights it implies ``skinny=True`` with the bound at 64.
 
+    ``activations="mxfp8"`` (off by default; ``weights="mxfp4"`` only, else ValueError): linear layers of
+    more than 16 rows quantise their input rows to MXFP8 (e4m3 with one e8m0 scale per 32 k) and multiply
+    the stored MXFP4 matrices on the scaled MFMA (:func:`ops.quant.linear_mx4a8`); the dequantisation
+    scratch is then never allocated.  Layers of at most 16 rows keep bf16 activations, so a verifying
+    ``extend`` of more than 16 rows and one-row decode steps round differently.
+
     ``kv_cache="int8"``: the caches :meth:`new_cache` makes (and so those of the ``generate*``
     methods) hold int8 rows (:class:`KVCache`); any kind of weights."""
 
     def __init__(self, cfg: NativeConfig, device, dtype=torch.bfloat16, seed: int = 0, init: bool = True,
-                 weights: str = "bf16", skinny: bool = False, kv_cache: str = "bf16", skinny64: bool = False):
+                 weights: str = "bf16", skinny: bool = False, kv_cache: str = "bf16", skinny64: bool = False,
+                 activations: str = "bf16"):
         _check_generative(cfg)
-        _check_weights(weights, skinny)
+        _check_weights(weights, skinny, activations)
         self.kv_cache = _check_kv(kv_cache)
         cfg = dataclasses.replace(cfg, dropout=0.0)
         if weights != "bf16":
@@ -329,7 +340,7 @@ class Generator:
             if init:
                 qw.init_params(seed)
             self._bind_quant(qw)
-            self.skinny64 = bool(skinny64)
+            self.skinny64, self.activations = bool(skinny64), activations
             return
         self._bind(NativeModel(cfg, 0, 1, torch.device(device), seed=seed, recompute=False, dtype=dtype, init=init))
         self.skinny, self.skinny64 = bool(skinny or skinny64), bool(skinny64)
@@ -343,7 +354,8 @@ class Generator:
         self.blocks: List[Block] = model.blocks
         self.weights = "bf16"
         self.skinny = self.skinny64 = False
-        self._scratch = None
+        self.activations = "bf16"
+        self._scratch = self._xq = None
 
     def _bind_quant(self, qw: QuantWeights) -> None:
         cfg = qw.cfg
@@ -358,19 +370,24 @@ class Generator:
         self.blocks = [_QBlock(i, qw, rope) for i in range(cfg.n_layers)]
         self.weights = qw.fmt
         self.skinny = self.skinny64 = False
+        self.activations = "bf16"
         self._scratch: Optional[torch.Tensor] = None
+        self._xq: Optional[torch.Tensor] = None         # the MXFP8 rows of the layer being computed
+        self._xq_retired: List[torch.Tensor] = []
+        self._xq_row_bytes = ops.quant.mx8_row_bytes(max(qw.specs[n].shape[1] for n in qw.order if qw.quantized(n))) \
+            if qw.fmt == "mxfp4" else 0
 
     # ------------------------------------------------------------------ constructors
     @classmethod
     def from_model(cls, model: NativeModel, weights: str = "bf16", skinny: bool = False,
-                   kv_cache: str = "bf16", skinny64: bool = False) -> "Generator":
+                   kv_cache: str = "bf16", skinny64: bool = False, activations: str = "bf16") -> "Generator":
         """Wrap an existing single-stage model (``trainer.stages[0].model`` at ``pp = 1``).
         With bf16 weights they are the model's arena itself: nothing is copied, and a later
         optimizer step is seen by the generator.  ``weights="int8"`` / ``"int4g128"`` take a quantised
         snapshot of the master weights instead: the model is left untouched, and the
         generator does NOT see later optimizer steps (build a new one after training on)."""
         _check_generative(model.cfg)
-        _check_weights(weights, skinny)
+        _check_weights(weights, skinny, activations)
         if model.num_stages != 1 or model.split_head:
             raise ValueError("Generator.from_model needs a single-stage model that owns its LM head (pp = 1)")
         self = cls.__new__(cls)
@@ -381,7 +398,7 @@ class Generator:
                 for n in qw.order:
                     qw.put(n, model.arena.master_view(n))
             self._bind_quant(qw)
-            self.skinny64 = bool(skinny64)
+            self.skinny64, self.activations = bool(skinny64), activations
             return self
         self._bind(model)
         self.skinny, self.skinny64 = bool(skinny or skinny64), bool(skinny64)
@@ -389,7 +406,7 @@ class Generator:
 
     @classmethod
     def load(cls, path: str, device=None, dtype=None, weights: str = "bf16", skinny: bool = False,
-             kv_cache: str = "bf16", skinny64: bool = False) -> "Generator":
+             kv_cache: str = "bf16", skinny64: bool = False, activations: str = "bf16") -> "Generator":
         """Weights-only load of a checkpoint directory written by ``save_checkpoint`` at any
         PP / DP degree or head mode (the tensors are found by FQN).  Defaults: the GPU in
         bf16 when there is one, else the CPU in f32.  ``weights="int8"`` / ``"int4g128"`` quantise
@@ -403,7 +420,7 @@ class Generator:
         if dtype is None:
             dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
         self = cls(cfg, device, dtype=dtype, init=False, weights=weights, skinny=skinny, kv_cache=kv_cache,
-                   skinny64=skinny64)
+                   skinny64=skinny64, activations=activations)
         if weights != "bf16":
             for name, t in iter_weights(path, self.arena.order):
                 self.arena.put(name, t)
@@ -419,6 +436,8 @@ class Generator:
         if self.weights != "bf16":
             key = A.head_name if wname == "lm_head" else wname
             q, scale = A.q[key], A.scale[key]
+            if self.activations == "mxfp8" and x.shape[0] > ops.W8_SKINNY_MAX_M:
+                return ops.quant.linear_mx4a8(x, q, scale, bias, act, residual, out, xq=self._xq_rows(x))
             scratch = None
             if x.is_cuda and not ops.quant.reads_weights_directly(x, self.weights, self.skinny64):
                 if self._scratch is None:
@@ -437,6 +456,22 @@ class Generator:
             if self.skinny64 and ops.quant.reads_weights_directly(x, "int8", True):
                 return ops.quant.linear_skinny64(x, w, None, bias, act, residual, out)
         return ops.linear(x, w, bias, act=act, residual=residual, out=out)[0]
+
+    def _xq_rows(self, x: torch.Tensor) -> Optional[torch.Tensor]:
+        """The generator's buffer of MXFP8 activation rows for the rows of ``x`` at the widest K of any
+        quantised matrix.  It only ever grows, outside a capture, and a buffer it outgrows is kept alive: a
+        graph captured around an earlier call keeps replaying into memory the generator still owns."""
+        if not x.is_cuda:
+            return None
+        need = x.shape[0] * self._xq_row_bytes
+        if self._xq is None or self._xq.numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("Generator: the MXFP8 activation rows cannot be allocated inside a graph capture "
+                                   "(run one step eagerly first)")
+            if self._xq is not None:
+                self._xq_retired.append(self._xq)
+            self._xq = torch.empty(need, device=self.device, dtype=ops.quant.FP8)
+        return self._xq
 
     # ------------------------------------------------------------------ cache
     def new_cache(self, B: int, max_len: Optional[int] = None, kv: Optional[str] = None) -> KVCache:

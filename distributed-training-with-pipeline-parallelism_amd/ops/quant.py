@@ -231,6 +231,100 @@ def dequant_mx4(q4: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tenso
     return out
 
 
+# mxfp8 activation rows: e4m3 elements with one e8m0 scale per 32 k, the scales inside the row (as in the int8 KV
+# cache), for the scaled-MFMA GEMM against MXFP4 weights (csrc/kernels/gemm_mx.hip).  Names of this module only
+FP8 = torch.float8_e4m3fn
+E4M3_MAX = 448.0
+
+
+def mx8_row_bytes(K: int) -> int:
+    """bytes of one MXFP8 row: K codes, K / 32 scale bytes, zero padding to a multiple of 16"""
+    return (K + K // MX_GROUP + 15) // 16 * 16
+
+
+def _mx8_rows(x: torch.Tensor) -> torch.Tensor:
+    """the rows of :func:`quantize_mx8_rows` as uint8 [M, mx8_row_bytes(K)]: tensor code, any device"""
+    M, K = x.shape
+    G = K // MX_GROUP
+    xf = x.detach().float().reshape(M, G, MX_GROUP)
+    amax = xf.abs().amax(dim=2)
+    E = (torch.frexp(amax)[1].to(torch.int32) - 9).clamp_(-127, 127)       # amax = m 2^ex, m in [0.5, 1)
+    # 2^-E from its bits (E <= 120: the exponent field stays in [7, 254]), so the products are exact
+    E = E + (amax * ((127 - E) << 23).view(torch.float32) > E4M3_MAX).to(torch.int32)
+    live = amax > 0
+    inv = torch.where(live, ((127 - E) << 23).view(torch.float32), torch.zeros_like(amax))
+    code = (xf * inv[:, :, None]).to(FP8).view(torch.uint8).reshape(M, K)
+    rows = torch.zeros(M, mx8_row_bytes(K), device=x.device, dtype=torch.uint8)
+    rows[:, :K] = torch.where(code == 0x80, torch.zeros_like(code), code)  # -0 is stored as 0
+    rows[:, K: K + G] = torch.where(live, E + 127, torch.zeros_like(E)).to(torch.uint8)
+    return rows
+
+
+def quantize_mx8_rows(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MXFP8 rows of ``x [M, K]`` (bf16 or f32 rows of any stride, ``K % 128 == 0``, else ValueError) ->
+    ``torch.float8_e4m3fn [M, mx8_row_bytes(K)]``, contiguous.  Bytes ``[0, K)`` of a row are OCP e4m3
+    codes in k order, bytes ``[K, K + K / 32)`` the e8m0 byte of each group of 32 (``e`` stands for
+    ``2^(e - 127)``), the rest zeros.  Per group, in f32: ``E = floor(log2 amax) - 8``, plus 1 if
+    ``amax * 2^-E > 448``, clamped to [-127, 127]; each element is ``x * 2^-E`` (exact) rounded to nearest
+    even into e4m3, subnormals kept, so no element exceeds 448 and nothing saturates.  A group of zeros
+    gets byte 0 and codes 0; a value that rounds to zero gets code 0; byte 255 is never written.  On the
+    GPU one kernel writes exactly these bytes: no synchronisation and, given ``out``, no allocation."""
+    if x.dim() != 2 or x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("quantize_mx8_rows: x must be bf16 or f32 [M, K]")
+    M, K = x.shape
+    if M < 1 or K < W4_GROUP or K % W4_GROUP != 0:
+        raise ValueError(f"quantize_mx8_rows: K = {K} must be a multiple of {W4_GROUP}")
+    if out is None:
+        out = torch.empty(M, mx8_row_bytes(K), device=x.device, dtype=FP8)
+    if out.dtype != FP8 or tuple(out.shape) != (M, mx8_row_bytes(K)) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"quantize_mx8_rows: out must be contiguous float8_e4m3fn [{M}, {mx8_row_bytes(K)}] on x's device")
+    if _gpu(x):
+        _ext().cast_f32_bf16(x, out)
+    else:
+        out.view(torch.uint8).copy_(_mx8_rows(x))
+    return out
+
+
+def dequantize_mx8_rows(xq: torch.Tensor, K: int, dtype=torch.float32) -> torch.Tensor:
+    """``[M, K]`` values of MXFP8 rows: e4m3(code) * 2^(byte - 127), exact in f32."""
+    if xq.dtype != FP8 or xq.dim() != 2 or K % MX_GROUP != 0 or xq.shape[1] != mx8_row_bytes(K):
+        raise ValueError(f"dequantize_mx8_rows: float8_e4m3fn [M, {mx8_row_bytes(K)}] rows needed, got {xq.dtype} "
+                         f"{tuple(xq.shape)}")
+    e8 = torch.tensor([2.0 ** (e - 127) for e in range(255)] + [float("nan")], device=xq.device)
+    s = e8[xq.view(torch.uint8)[:, K: K + K // MX_GROUP].to(torch.int64)]
+    return (xq[:, :K].float() * s.repeat_interleave(MX_GROUP, dim=1)).to(dtype)
+
+
+def _mx4a8_matmul_cpu(x, q4, scale):
+    xh = dequantize_mx8_rows(quantize_mx8_rows(x.detach()), x.shape[1])
+    return (xh.double() @ _mx4_what(q4, scale).double().t()).float()
+
+
+def linear_mx4a8(x: torch.Tensor, q4: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                 act: str = "none", residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                 xq: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = act(Xhat @ What^T + bias) (+ residual) for any number of rows, with ``Xhat`` the MXFP8 rows of
+    ``x`` (:func:`quantize_mx8_rows`) and ``What`` MXFP4 weights as :func:`quantize_mx4` stores them.  On
+    the GPU two kernels: the quantiser into ``xq`` (a contiguous float8_e4m3fn buffer of at least
+    ``M * mx8_row_bytes(K)`` elements; allocated here if None), then the GEMM on
+    v_mfma_scale_f32_16x16x128_f8f6f4, which reads both operands as stored and accumulates in f32.  No
+    scratch, no synchronisation, and with ``out`` and ``xq`` no allocation.  Row m of the result does not
+    depend on M or on the other rows.  On the CPU: the product of the two dequantised operands, with the
+    epilogue of the other quantised linears.  Returns y."""
+    f = MX_FORMATS["mxfp4"]
+    M, N, K, out = _checked("linear_mx4a8", f, x, q4, scale, bias, act, residual, out)
+    if not _gpu(x):
+        return _linear_cpu(f._replace(matmul_cpu=_mx4a8_matmul_cpu), x, q4, scale, bias, act, residual, out)
+    need = M * mx8_row_bytes(K)
+    if xq is None:
+        xq = torch.empty(need, device=x.device, dtype=FP8)
+    if xq.dtype != FP8 or not xq.is_contiguous() or xq.numel() < need:
+        raise ValueError(f"linear_mx4a8: xq must be contiguous float8_e4m3fn with at least {need} elements")
+    rows = quantize_mx8_rows(x, out=xq.view(-1)[:need].view(M, -1))
+    _ext().gemv_skinny(rows, q4, scale, out, bias, residual, act != "none", 0)
+    return out
+
+
 # One entry per format, holding what differs: the operand check (name, x, q, scale); x @ What^T in f32 on the CPU,
 # scaled in the kernel's order; quantize and dequant; the K multiple a matrix needs to be stored (k_format) and to be
 # read by the skinny kernel (k_skinny); the names its errors carry and where the skinny kernel's M bound points

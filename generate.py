@@ -38,6 +38,10 @@ pass of speculative decoding, a short prefill) on the 64-row weight-streaming ke
 
 ``--kv-cache int8`` keeps the K / V cache as int8 rows with one f32 scale per (token, KV head):
 about half the cache bytes, with any ``--weights`` (the draft follows ``--draft-kv-cache``).
+
+``--activations mxfp8`` (with ``--weights mxfp4`` only): linear layers of more than 16 rows quantise their
+input rows to MXFP8 and multiply the stored MXFP4 matrices on the scaled MFMA, with no dequantisation
+scratch; off by default.
 """
 from __future__ import annotations
 
@@ -79,6 +83,8 @@ def main(argv=None) -> int:
     ap.add_argument("--skinny64", action="store_true",
                     help="linear layers of 17 to 64 rows on the 64-row weight-streaming kernel (no dequantisation "
                     "scratch for them); also for the draft model")
+    ap.add_argument("--activations", choices=("bf16", "mxfp8"), default="bf16",
+                    help="mxfp8 (needs --weights mxfp4): layers of more than 16 rows run the MXFP8 x MXFP4 GEMM")
     a = ap.parse_args(argv)
 
     import torch
@@ -86,7 +92,7 @@ def main(argv=None) -> int:
 
     rows = parse_prompts(a.prompt)
     gen = mipipe.Generator.load(a.checkpoint, device=a.device, weights=a.weights, kv_cache=a.kv_cache,
-                                skinny64=a.skinny64)
+                                skinny64=a.skinny64, activations=a.activations)
     bad = [t for r in rows for t in r if not 0 <= t < gen.cfg.vocab_size]
     if bad:
         raise ValueError(f"--prompt: token id {bad[0]} outside the vocabulary [0, {gen.cfg.vocab_size})")

@@ -44,7 +44,11 @@ FILE_FLAGS = {"attention.hip": ["-fno-slp-vectorize"], "attention_doc.hip": ["-f
               # these have been seen to return wrong values on MI355X without an error.  Not a speed
               # choice, and the bit-equality with gemv_skinny.hip does not rest on it -- an FMA per
               # element either way, and tests/test_gemv_rows64_gpu.py compares the bits as built
-              "gemv_rows64.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "gemv_rows64.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # the same rule for gemm_mx.hip (its f32 arithmetic is the quantiser's 32 multiplies per lane and
+              # the GEMM's epilogue).  Its tests -- the quantiser's bytes, the exact all-codes product -- were
+              # run as built, with the flag, and never without it
+              "gemm_mx.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _torch_paths():

@@ -5,6 +5,7 @@ generators, on one GPU.
     python tools/w8_time.py                       # both tables (profiles/r12_w8_decode.md, r13_w4_decode.md)
     python tools/w8_time.py --parts gemm --models llama3-1b --rows 1,16
     python tools/w8_time.py --parts e2e --batches 1 --speculative
+    python tools/w8_time.py --parts mx,mx_e2e --models llama3-1b,llama3-8b --iters 50     # profiles/r17_gemm_mx.md
 
 Needs a GPU and the built extension: there is no fallback.  The protocol is that of
 tools/generate_time.py: per shape every variant is warmed, then the variants alternate inside
@@ -138,6 +139,111 @@ def gemm_part(a, dev):
     return recs
 
 
+def mx_part(a, dev):
+    """``--parts mx`` (profiles/r17_gemm_mx.md): per shape and M in ``--mx-rows``, ``mx4a8`` = ops.quant.linear_mx4a8
+    (quantiser + the MXFP8 x MXFP4 GEMM), ``mx4a8_gemm`` = the GEMM alone on rows quantised before the window,
+    ``mx4`` = ops.quant.linear_mx4 (dequantise + ops.linear above 16 rows) and ``linear`` = ops.linear on bf16
+    weights, alternating in the same windows; and the plan's tile."""
+    recs = []
+    Q = ops.quant
+    for mname in a.models.split(","):
+        for lname, (N, K) in zip(NAMES, MODEL_SHAPES[mname]):
+            copies = max(2, min(64, -(-a.cold_mb * (1 << 20) // (N * K))))
+            w = [torch.randn(N, K, device=dev, dtype=torch.bfloat16) * (K ** -0.5) for _ in range(copies)]
+            mxs = [Q.quantize_mx4(t) for t in w]
+            scratch = torch.empty(N * K, device=dev, dtype=torch.bfloat16)
+            for M in (int(m) for m in a.mx_rows.split(",")):
+                x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
+                y = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+                xq = Q.quantize_mx8_rows(x)
+                gemm = ops.load_ext().gemv_skinny
+                variants = {
+                    "mx4a8": lambda i: Q.linear_mx4a8(x, *mxs[i % copies], out=y, xq=xq),
+                    "mx4a8_gemm": lambda i: gemm(xq, *mxs[i % copies], y, None, None),
+                    "mx4": lambda i: Q.linear_mx4(x, *mxs[i % copies], out=y, scratch=scratch),
+                    "linear": lambda i: ops.linear(x, w[i % copies], out=y),
+                }
+                t, spread = _windows(variants, a.windows, a.iters)
+                rec = {"model": mname, "layer": lname, "N": N, "K": K, "M": M, "copies": copies,
+                       "tile": "64x32" if M <= 64 else "128x128"}
+                for name, sec in t.items():
+                    rec[f"{name}_us"] = round(sec * 1e6, 1)
+                    rec[f"{name}_spread_us"] = round(spread[name] * 1e6, 1)
+                rec["tflops_gemm"] = round(2.0 * M * N * K / t["mx4a8_gemm"] * 1e-12, 1)
+                print(json.dumps(rec), flush=True)
+                recs.append(rec)
+            del w, mxs, scratch
+            torch.cuda.empty_cache()
+    return recs
+
+
+def mx_e2e_part(a, dev):
+    """``--parts mx_e2e`` (profiles/r17_gemm_mx.md).  Llama-3 1B, ``--mx-prompt`` prompt tokens, ``--mx-new`` new
+    tokens, B = ``--mx-batch``: peak allocated bytes of a ``weights="mxfp4"`` generator with and without
+    ``activations="mxfp8"`` over one ``generate_batch`` (each alone on the device), then tokens/s of both and of
+    the bf16 generator, alternating, one whole call per window.  Then the logit error of a random-init GPT-2
+    small against its bf16 generator (B = 4, 96-token prefill, 32 teacher-forced decode steps)."""
+    S0, N, B = a.mx_prompt, a.mx_new, a.mx_batch
+    cfg = NativeConfig.llama3("1b", max_seq_len=S0 + N + 64)
+    rows = list(torch.randint(0, cfg.vocab_size, (B, S0), generator=torch.Generator().manual_seed(B)))
+    kinds = {"mxfp4": {"weights": "mxfp4"}, "mxfp4_mxfp8": {"weights": "mxfp4", "activations": "mxfp8"}, "bf16": {}}
+    rec = {"model": "llama3-1b", "B": B, "prompt": S0, "new_tokens": N}
+    for n in ("mxfp4", "mxfp4_mxfp8"):
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        g = mipipe.Generator(cfg, dev, dtype=torch.bfloat16, seed=0, **kinds[n])
+        rec[f"{n}_weights_bytes"] = torch.cuda.memory_allocated()
+        g.generate_batch(rows, N, graphs=False)
+        torch.cuda.synchronize()
+        rec[f"{n}_peak_bytes"] = torch.cuda.max_memory_allocated()
+        rec[f"{n}_scratch"] = None if g._scratch is None else g._scratch.numel() * 2
+        del g
+    gens = {n: mipipe.Generator(cfg, dev, dtype=torch.bfloat16, seed=0, **kw) for n, kw in kinds.items()}
+    times = {n: [] for n in gens}
+    for w in range(a.windows + 1):                                      # window 0 warms
+        for n, g in gens.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            g.generate_batch(rows, N, graphs=False)
+            torch.cuda.synchronize()
+            if w:
+                times[n].append(time.perf_counter() - t0)
+    for n in gens:
+        rec[f"{n}_ms"] = round(statistics.median(times[n]) * 1e3, 1)
+        rec[f"{n}_spread_ms"] = round((max(times[n]) - min(times[n])) * 1e3, 1)
+        rec[f"{n}_tok_s"] = round(B * N / statistics.median(times[n]), 1)
+    # the prefill alone (the part the option changes at B <= 16)
+    for n, g in gens.items():
+        ts = []
+        for _ in range(a.windows):
+            cache = g.new_cache(B, S0 + 8)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            g.prefill(torch.stack(rows).to(dev), cache)
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        rec[f"{n}_prefill_ms"] = round(statistics.median(ts) * 1e3, 1)
+    print(json.dumps(rec), flush=True)
+    del gens
+    torch.cuda.empty_cache()
+    cfg = NativeConfig.gpt2("small")
+    tok = torch.randint(0, cfg.vocab_size, (4, 128), generator=torch.Generator().manual_seed(4)).to(dev)
+    lg = {}
+    for n, kw in kinds.items():
+        g = mipipe.Generator(cfg, dev, dtype=torch.bfloat16, seed=0, **kw)
+        cache = g.new_cache(4, 128)
+        out = [g.prefill(tok[:, :96].contiguous(), cache)] + [g.decode(tok[:, t].contiguous(), cache) for t in range(96, 128)]
+        lg[n] = torch.stack(out, 1)[..., : cfg.vocab_size].float()
+        del g, cache
+    err = {"protocol": "gpt2-small random init, B 4, 96-token prefill + 32 decode steps, against the bf16 generator",
+           "logit_rms": round(float(lg["bf16"].pow(2).mean().sqrt()), 3)}
+    for n in ("mxfp4", "mxfp4_mxfp8"):
+        d = lg[n] - lg["bf16"]
+        err[n] = {"max": round(float(d.abs().max()), 3), "rms": round(float(d.pow(2).mean().sqrt()), 3),
+                  "same_argmax": round(float((lg[n].argmax(-1) == lg["bf16"].argmax(-1)).float().mean()), 3)}
+    print(json.dumps(err), flush=True)
+
+
 def e2e_part(a, dev):
     recs = []
     S0, N = a.prompt, a.new_tokens
@@ -227,6 +333,10 @@ def main(argv=None) -> int:
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--cold-mb", type=int, default=512)
     ap.add_argument("--speculative", action="store_true")
+    ap.add_argument("--mx-rows", default="32,64,256,2048", help="rows of --parts mx")
+    ap.add_argument("--mx-prompt", type=int, default=4096, help="prompt tokens of --parts mx_e2e")
+    ap.add_argument("--mx-new", type=int, default=64)
+    ap.add_argument("--mx-batch", type=int, default=8)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available() or not ops.ext_available():
         raise SystemExit("w8_time: needs a GPU and the built HIP extension")
@@ -237,6 +347,10 @@ def main(argv=None) -> int:
     parts = a.parts.split(",")
     gemm = gemm_part(a, dev) if "gemm" in parts else []
     e2e = e2e_part(a, dev) if "e2e" in parts else []
+    if "mx" in parts:
+        mx_part(a, dev)
+    if "mx_e2e" in parts:
+        mx_e2e_part(a, dev)
     _markdown(gemm, e2e)
     return 0
 
