@@ -20,6 +20,28 @@ struct GemvArgs {
   int64_t ldx, ldy, ldr;
 };
 
+// The C entries' arguments as GemvArgs.  False: w is not 16-byte aligned (every kernel reads a
+// lane's weights of a step as 16-byte loads).  What a scale must be is the entry's own condition.
+inline bool gemv_args(GemvArgs& a, const void* w, const void* scale, const void* x, void* y, const void* bias,
+                      const void* res, int M, int N, int K, int64_t ldx, int64_t ldy, int64_t ldr, int gelu) {
+  a.w = w, a.scale = (const float*)scale, a.x = (const bf16_t*)x, a.y = (bf16_t*)y;
+  a.bias = (const bf16_t*)bias, a.res = (const bf16_t*)res;
+  a.M = M, a.N = N, a.K = K, a.gelu = gelu, a.ldx = ldx, a.ldy = ldy, a.ldr = ldr;
+  return ((uintptr_t)w & 15) == 0;
+}
+
+// The f32 epilogue of one result element, y[m, n] = bf16(epi(v)): the per-row scale (int8
+// weights), bias, GELU on the bf16-rounded pre-activation (as the bf16 GEMM's epilogue takes it:
+// mp_gemm_core.h), residual.  One copy for every kernel here, so a row's bits cannot depend on
+// which of them ran.
+__device__ __forceinline__ void gemv_store(const GemvArgs& a, float v, int m, int64_t n, bool row_scale) {
+  if (row_scale) v *= a.scale[n];
+  if (a.bias) v += bf2f(a.bias[n]);
+  if (a.gelu) v = gelu_tanh(IO8<bf16_t>::get_round(v));
+  if (a.res) v += bf2f(a.res[(int64_t)m * a.ldr + n]);
+  a.y[(int64_t)m * a.ldy + n] = f2bf(v);
+}
+
 // the lane's 32 weights of one step as four MFMA fragments
 template <typename WT>
 struct WFrag;

@@ -31,7 +31,7 @@
 // bytes (x: 144, w: 80) so the 16 rows a b128 read touches spread over the banks.  The x scale
 // dword of a step is always 4-byte aligned (rows are 16-byte aligned and K % 128 == 0); the
 // weight scale table may sit at any address, and is read as dwords when it is 4-byte aligned and
-// as bytes otherwise (SA), as gemv_mx4_kernel does.
+// as bytes otherwise (SA), as the skinny kernel's MX4Fmt does.
 //
 // Bounds.  Tile rows past M and columns past N load row M - 1 / N - 1 again (an address inside
 // the operand) and are never stored.  No array content becomes an address.  No allocation, no

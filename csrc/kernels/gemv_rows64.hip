@@ -281,13 +281,7 @@ __global__ __launch_bounds__(G == 1 ? 1024 : 512) void gemv_rows64_kernel(GemvAr
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t n = nl + 16 * g + r;
-        if (n >= a.N) continue;
-        float v = acc[g][t][r];
-        if constexpr (WB == 1) v *= a.scale[n];
-        if (a.bias) v += bf2f(a.bias[n]);
-        if (a.gelu) v = gelu_tanh(IO8<bf16_t>::get_round(v));
-        if (a.res) v += bf2f(a.res[(int64_t)m * a.ldr + n]);
-        a.y[(int64_t)m * a.ldy + n] = f2bf(v);
+        if (n < a.N) gemv_store(a, acc[g][t][r], m, n, WB == 1);
       }
   }
 }
@@ -325,11 +319,9 @@ extern "C" int mp_gemv_rows64(const void* w, const float* scale, int wbytes, con
                               int force_split, hipStream_t st) {
   const gemv::Plan p = gemv::plan_rows64(N, K, wbytes, M, force_split);
   if (p.rows == 0) return -1;
-  if ((wbytes != 2) != (scale != nullptr) || ((uintptr_t)w & 15) || ((uintptr_t)scale & 3)) return -1;
   mp::GemvArgs a;
-  a.w = w, a.scale = scale, a.x = (const mp::bf16_t*)x, a.y = (mp::bf16_t*)y;
-  a.bias = (const mp::bf16_t*)bias, a.res = (const mp::bf16_t*)res;
-  a.M = M, a.N = N, a.K = K, a.gelu = gelu, a.ldx = ldx, a.ldy = ldy, a.ldr = ldr;
+  if (!mp::gemv_args(a, w, scale, x, y, bias, res, M, N, K, ldx, ldy, ldr, gelu)) return -1;
+  if ((wbytes != 2) != (scale != nullptr) || ((uintptr_t)scale & 3)) return -1;
   // x rows are read as 16-byte chunks at 32-bit offsets from a tile's first row
   if (((uintptr_t)x & 15) || ldx % 8 != 0 || ldx >= (int64_t)1 << 26) return -1;
   if (wbytes == 0) return mp::launch<0>(a, p, st);

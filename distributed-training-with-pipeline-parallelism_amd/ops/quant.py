@@ -148,7 +148,7 @@ def dequant_w4(q4: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor
     return out
 
 
-# mxfp4: OCP MXFP4 -- e2m1 elements with one e8m0 (power-of-two) scale per 32 k -- on gemv_mx4_kernel.  Names of
+# mxfp4: OCP MXFP4 -- e2m1 elements with one e8m0 (power-of-two) scale per 32 k -- on the skinny kernel (MX4Fmt of gemv_skinny.hip).  Names of
 # this module only
 MX_GROUP = 32
 _E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
